@@ -8,11 +8,14 @@ Workload = BASELINE.json config c3: 8 clips x 15 frames x 32 actors x 16 384 poi
 frames, fp32, synthetic data (multimodal_gar_amd/workload.py).  The 8 clips are the GLOBAL batch
 (config c4: "same config under DDP"), sharded over the ranks => strong scaling.
 
-Besides the headline number the line carries
+A plain run sets up, warms up, times --steps steps and prints the line; `roofline`, `cpu_baseline` and
+`step_accounting` are null in it.  With --full the line also carries
   roofline     : the dominant hand-written kernel of the step, timed live with events on the stream
                  it is launched on, against the bound DESIGN.md derives for it;
   cpu_baseline : the same model code on the host cores with the CPU oracle in place of the HIP
                  kernels (oracle/cpu_backend.py), on a bounded sample, rank 0 at N = 1 only.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, see dump_outputs().
 """
 import argparse
 import json
@@ -94,6 +97,14 @@ def parse():
                     help="input-side software pipelining (off by default): every step computes the PointNet++ trunk's coordinate-only "
                          "work (FPS, ball queries, 3-NN weights) for the NEXT batch on a side stream while it runs the feature path and "
                          "the backward of the current one; the same work per step, the level-1 FPS off the critical path")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the instrumented eager step "
+                         "behind `roofline` / `step_accounting` and the per-kernel table (unless --no-kernel-timing), and the "
+                         "CPU baseline (unless --no-cpu-baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all; "
+                         "larger arrays as a fixed, seeded sample): the loss, the updated trainable parameters and their "
+                         "gradients of a training step, the outputs of a forward step")
     ap.add_argument("--phases", action="store_true", help="print a synchronised per-phase timing of one step")
     ap.add_argument("--kernels-out", default=None,
                     help="where the per-kernel roofline table of the instrumented step is written (default: "
@@ -357,6 +368,58 @@ def write_kernel_table(path, kernels, accounting, header):
                                                        ("%.0f %s = %.2f of peak" % (r["achieved"], r["unit"], r["frac"])) if "frac" in r else ""))
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0
+
+
+def step_outputs(step, result):
+    """-> [(name, tensor)]: what a caller of the timed step holds after its last run.  A training step: the loss it returned,
+    the trainable parameters after the optimizer update and the gradients that update used (both flattened in parameter
+    order; a parameter without a gradient counts as zeros); a forward step: the tensors it returned."""
+    if hasattr(step, "params") and hasattr(step, "opt"):
+        grads = [p.grad.detach() if p.grad is not None else torch.zeros_like(p) for p in step.params]
+        return [("loss", result.detach()), ("params", torch.cat([p.detach().reshape(-1) for p in step.params])),
+                ("grads", torch.cat([g.reshape(-1) for g in grads]))]
+    if isinstance(step, StubStep):
+        return [("exchanged", step.flat)]
+    out = []
+
+    def walk(x, name):
+        if torch.is_tensor(x):
+            out.append((name, x.detach()))
+        elif isinstance(x, dict):
+            for k, v in x.items():
+                walk(v, "%s.%s" % (name, k))
+        elif isinstance(x, (list, tuple)):
+            for i, v in enumerate(x):
+                walk(v, "%s.%d" % (name, i))
+    walk(result, "out")
+    return out
+
+
+def dump_outputs(directory, named):
+    """Writes every (name, tensor) as directory/<name>.npy: floating tensors as float32 (float64 stays float64), integer /
+    bool ones as float64.  An array larger than its share of DUMP_LIMIT_BYTES is written as a fixed sample: the elements
+    at sorted indices drawn without replacement by numpy's default_rng(DUMP_SAMPLE_SEED), the same for the same size.
+    -> {file name: number of elements written}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(named), 1)
+    written = {}
+    for name, t in named:
+        t = t.reshape(-1)
+        dtype = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        cap = share // (8 if dtype == torch.float64 else 4)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(t.numel(), cap, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.to(dtype).cpu().numpy()
+        safe = "".join(c if (c.isalnum() or c in "._-") else "_" for c in name)
+        np.save(os.path.join(directory, safe + ".npy"), a)
+        written[safe] = a.size
+    return written
+
+
 def spawn_command(n_gpus, argv, port=None):
     """`python bench.py --gpus N` outside a launcher: the command that starts the N ranks (one per GPU) as a CHILD process --
     never an exec, and before torch / the package / anything that touches the GPU is imported in this process."""
@@ -487,7 +550,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step.run(batch)
+        result = step.run(batch)
         if rank == 0:
             log("timed step %d issued" % i)   # host-side only: no sync inside the timed region
     barrier()
@@ -500,9 +563,13 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = args.clips * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: these are the arrays of the last timed one
+        written = dump_outputs(args.dump_outputs, step_outputs(step, result))
+        log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, written))
 
     roof, kernels, cpu, accounting, kernels_file = None, None, None, None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # every rank issues the same two extra eager steps (their gradient exchanges are collective); rank 0 instruments its second
         rec = extra_steps(step, batch, instrument=(rank == 0 and not stub))
         if rec is not None:
@@ -512,7 +579,7 @@ def main():
                 % (roof["kernel"], roof["ms_per_step"], roof["launches_per_step"], roof["achieved"], roof["unit"], 100 * roof["frac"]))
             log("step accounting (ms): %s" % {k: (round(v, 1) if isinstance(v, float) else v) for k, v in accounting.items()})
         barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "train" and not stub:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "train" and not stub:
         cpu = cpu_baseline(args)
     if stub:
         counts = [step.collectives]

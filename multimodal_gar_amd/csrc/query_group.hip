@@ -78,42 +78,95 @@ __global__ __launch_bounds__(256) void qg_batch_fwd_kernel(int c, int n, int npo
     }
 }
 
-// grid: (c, b); one workgroup owns one (b, c) row of grad_features, accumulated in LDS
-__global__ __launch_bounds__(1024) void qg_batch_bwd_lds_kernel(int c, int n, int cols, const float *__restrict__ grad_y,
+// grid: (c, b); one workgroup owns one (b, c) row of grad_features, accumulated in LDS.
+// The scatter is order-free, so the result is the same from run to run: every contribution is added as a 64-bit fixed-point
+// integer g * 2^S (integer addition is associative), with S the largest exponent for which cols * max|g| * 2^S stays
+// below 2^62 (no overflow whatever the order), and the sum is converted back once.  A contribution is rounded by at most
+// 2^-S / 2 <= max|g| * cols * 2^-61, so a cell that k contributions reach is the exact sum, off by at most
+// k * max|g| * cols * 2^-61, rounded to fp32: an absolute error tiny against the row's largest term (not against a cell
+// that is itself tiny next to it), where a float scatter errs by fp32 roundings of its partial sums.  Float atomics made the
+// order -- and the low bits of the gradients -- depend on the timing of the waves.  The n cells are covered in windows of
+// `win` (the int64 row takes twice the LDS of a float row); a row with a non-finite gradient takes the float path.
+__global__ __launch_bounds__(1024) void qg_batch_bwd_lds_kernel(int c, int n, int cols, int win, const float *__restrict__ grad_y,
                                                                 size_t y_bstride, const int *__restrict__ idx,
                                                                 float *__restrict__ grad_features) {
-    extern __shared__ float row[];
+    extern __shared__ unsigned long long row64[];
+    float *rowf = reinterpret_cast<float *>(row64);
+    __shared__ int s_max_bits;
     const int ci = blockIdx.x, bs = blockIdx.y;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) row[i] = 0.f;
-    __syncthreads();
     const float *g = grad_y + (size_t)bs * y_bstride + (size_t)ci * cols;
     const int *id = idx + (size_t)bs * cols;
-    // 16-byte loads, two of them in flight per operand (round 3): the scalar version waited for one 4-byte index and one 4-byte
-    // gradient per LDS atomic and ran at the pace of the memory latency (0.7 ms per launch at level 1 of config c3)
-    if ((cols & 3) == 0 && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(id)) & 15) == 0) {
-        const int q = cols >> 2;
+    float *dst = grad_features + ((size_t)bs * c + ci) * n;
+    const bool vec = (cols & 3) == 0 && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(id)) & 15) == 0;
+    // max |g| of the row as the integer max of |g|'s bit pattern: non-negative floats order as integers and every NaN sorts
+    // above +inf, so one non-finite element anywhere in the row makes the maximum non-finite (integer max cannot forget it)
+    if (threadIdx.x == 0) s_max_bits = 0;
+    __syncthreads();
+    int mx = 0;
+    if (vec) {
         const float4 *g4 = reinterpret_cast<const float4 *>(g);
-        const int4 *i4 = reinterpret_cast<const int4 *>(id);
-        int e = threadIdx.x;
-        for (; e + (int)blockDim.x < q; e += 2 * blockDim.x) {
-            const int4 ia = i4[e], ib = i4[e + blockDim.x];
-            const float4 ga = g4[e], gb = g4[e + blockDim.x];
-            atomicAdd(&row[ia.x], ga.x); atomicAdd(&row[ia.y], ga.y); atomicAdd(&row[ia.z], ga.z); atomicAdd(&row[ia.w], ga.w);
-            atomicAdd(&row[ib.x], gb.x); atomicAdd(&row[ib.y], gb.y); atomicAdd(&row[ib.z], gb.z); atomicAdd(&row[ib.w], gb.w);
-        }
-        if (e < q) {
-            const int4 ia = i4[e];
-            const float4 ga = g4[e];
-            atomicAdd(&row[ia.x], ga.x); atomicAdd(&row[ia.y], ga.y); atomicAdd(&row[ia.z], ga.z); atomicAdd(&row[ia.w], ga.w);
+        for (int e = threadIdx.x; e < (cols >> 2); e += blockDim.x) {
+            const float4 v = g4[e];
+            mx = max(max(mx, max(__float_as_int(v.x) & 0x7fffffff, __float_as_int(v.y) & 0x7fffffff)),
+                     max(__float_as_int(v.z) & 0x7fffffff, __float_as_int(v.w) & 0x7fffffff));
         }
     } else {
-        for (int e = threadIdx.x; e < cols; e += blockDim.x) atomicAdd(&row[id[e]], g[e]);
+        for (int e = threadIdx.x; e < cols; e += blockDim.x) mx = max(mx, __float_as_int(g[e]) & 0x7fffffff);
     }
+    atomicMax(&s_max_bits, mx);
     __syncthreads();
-    float *dst = grad_features + ((size_t)bs * c + ci) * n;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float v = row[i];
-        if (v != 0.f) dst[i] += v;
+    const float gmax = __int_as_float(s_max_bits);
+    if (gmax == 0.f) return;                      // nothing to add
+    if (s_max_bits >= 0x7f800000) {               // inf / NaN: propagate it as the float scatter does (n <= 2 * win here)
+        for (int i = threadIdx.x; i < n; i += blockDim.x) rowf[i] = 0.f;
+        __syncthreads();
+        for (int e = threadIdx.x; e < cols; e += blockDim.x)
+            if ((unsigned)id[e] < (unsigned)n) atomicAdd(&rowf[id[e]], g[e]);
+        __syncthreads();
+        for (int i = threadIdx.x; i < n; i += blockDim.x)
+            if (rowf[i] != 0.f) dst[i] += rowf[i];
+        return;
+    }
+    int e_max, e_cols;
+    (void)frexpf(gmax, &e_max);                   // gmax < 2^e_max
+    (void)frexpf((float)cols, &e_cols);           // cols < 2^e_cols
+    const int S = 62 - e_max - e_cols;            // |row sum| < 2^(e_max + e_cols) * 2^S = 2^62
+    auto add = [&](int i, float v, int w0, int wn) {
+        const int k = i - w0;
+        if (k >= 0 && k < wn && v != 0.f)
+            atomicAdd(&row64[k], (unsigned long long)__double2ll_rn(ldexp((double)v, S)));
+    };
+    for (int w0 = 0; w0 < n; w0 += win) {
+        const int wn = min(win, n - w0);
+        for (int i = threadIdx.x; i < wn; i += blockDim.x) row64[i] = 0ull;
+        __syncthreads();
+        // 16-byte loads, two of them in flight per operand (round 3): the scalar version waited for one 4-byte index and one
+        // 4-byte gradient per LDS atomic and ran at the pace of the memory latency (0.7 ms per launch at level 1 of config c3)
+        if (vec) {
+            const int q = cols >> 2;
+            const float4 *g4 = reinterpret_cast<const float4 *>(g);
+            const int4 *i4 = reinterpret_cast<const int4 *>(id);
+            int e = threadIdx.x;
+            for (; e + (int)blockDim.x < q; e += 2 * blockDim.x) {
+                const int4 ia = i4[e], ib = i4[e + blockDim.x];
+                const float4 ga = g4[e], gb = g4[e + blockDim.x];
+                add(ia.x, ga.x, w0, wn); add(ia.y, ga.y, w0, wn); add(ia.z, ga.z, w0, wn); add(ia.w, ga.w, w0, wn);
+                add(ib.x, gb.x, w0, wn); add(ib.y, gb.y, w0, wn); add(ib.z, gb.z, w0, wn); add(ib.w, gb.w, w0, wn);
+            }
+            if (e < q) {
+                const int4 ia = i4[e];
+                const float4 ga = g4[e];
+                add(ia.x, ga.x, w0, wn); add(ia.y, ga.y, w0, wn); add(ia.z, ga.z, w0, wn); add(ia.w, ga.w, w0, wn);
+            }
+        } else {
+            for (int e = threadIdx.x; e < cols; e += blockDim.x) add(id[e], g[e], w0, wn);
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < wn; i += blockDim.x) {
+            const long long q = (long long)row64[i];
+            if (q != 0) dst[w0 + i] += (float)ldexp((double)q, -S);
+        }
+        __syncthreads();
     }
 }
 
@@ -965,8 +1018,10 @@ static int qg_batch_bwd(int b, int c, int n, int npoints, int nsample, const flo
                                       QG_LDS_MAX_FLOATS * (int)sizeof(float));
             attr_set = true;
         }
-        hipLaunchKernelGGL(qg_batch_bwd_lds_kernel, dim3(c, b), dim3(cols >= 4096 ? 1024 : 256), (size_t)n * sizeof(float),
-                           (hipStream_t)stream, c, n, cols, grad_y, y_bstride, idx, grad_features);
+        // int64 cells: windows of QG_LDS_MAX_FLOATS / 2 target points (one window up to n = 18432)
+        const int win = QG_LDS_MAX_FLOATS / 2;
+        hipLaunchKernelGGL(qg_batch_bwd_lds_kernel, dim3(c, b), dim3(cols >= 4096 ? 1024 : 256),
+                           (size_t)(n < win ? n : win) * sizeof(unsigned long long), (hipStream_t)stream, c, n, cols, win, grad_y, y_bstride, idx, grad_features);
     } else {
         hipLaunchKernelGGL(qg_batch_bwd_atomic_kernel, dim3(ceil_div(cols, 256), c, b), dim3(256), 0, (hipStream_t)stream, c, n,
                            cols, grad_y, y_bstride, idx, grad_features);

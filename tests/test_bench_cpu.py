@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -86,7 +87,7 @@ def test_gpus_2_without_launcher_runs_two_ranks_with_equal_collective_counts():
     """`python bench.py --gpus 2` with WORLD_SIZE unset must start two ranks itself (r2: it silently measured one), and the
     control flow around the timed region / the instrumented step must issue the same collectives on every rank (r2: rank 0
     issued one more gradient all-reduce than the others).  Driven end to end through main() with the stub step on gloo."""
-    p = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "2"],
+    p = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "2", "--full"],
                    {"MGAR_BENCH_STUB_STEP": "1", "MGAR_BENCH_BACKEND": "gloo", "OMP_NUM_THREADS": "1"})
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -95,6 +96,44 @@ def test_gpus_2_without_launcher_runs_two_ranks_with_equal_collective_counts():
     # warmup 2 + timed 3 + the two extra eager steps
     assert got["collectives_per_rank"] == [7, 7]
     assert len(lines[-1]) < 4096
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_issues_only_warmup_and_timed_steps():
+    """Without --full the benchmark runs no step beyond the warm-up and the --steps timed ones, on every rank."""
+    p = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1"],
+                   {"MGAR_BENCH_STUB_STEP": "1", "MGAR_BENCH_BACKEND": "gloo", "OMP_NUM_THREADS": "1"})
+    assert p.returncode == 0, p.stderr[-2000:]
+    got = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
+    assert got["steps"] == 4 and got["warmup"] == 1 and got["ms_per_step"] > 0
+    assert got["collectives_per_rank"] == [5, 5]
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    p = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                   {"MGAR_BENCH_STUB_STEP": "1", "MGAR_BENCH_BACKEND": "gloo", "OMP_NUM_THREADS": "1"})
+    assert p.returncode == 0, p.stderr[-2000:]
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["exchanged.npy"]
+    a = np.load(tmp_path / "out" / "exchanged.npy")
+    assert a.dtype == np.float32 and a.shape == (1 << 16,) and (a == 1).all()
+
+
+def test_dump_outputs_samples_large_arrays_reproducibly(tmp_path):
+    import torch
+    bench.torch = torch
+    big = torch.arange(20 << 20, dtype=torch.float64)                      # 160 MB: above the 64 MB limit on its own
+    named = [("loss", torch.tensor(1.5)), ("big", big), ("idx", torch.arange(7, dtype=torch.int64))]
+    w1 = bench.dump_outputs(str(tmp_path / "a"), named)
+    w2 = bench.dump_outputs(str(tmp_path / "b"), named)
+    assert w1 == w2 and w1["loss"] == 1 and w1["idx"] == 7 and 0 < w1["big"] < big.numel()
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= bench.DUMP_LIMIT_BYTES + 4096
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, b) and (np.diff(a) > 0).all()    # sorted, distinct elements of `big`
+    assert np.load(tmp_path / "a" / "idx.npy").dtype == np.float64
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.tolist() == [1.5]
 
 
 def test_world_size_must_match_gpus():

@@ -1,15 +1,14 @@
 """compat.install(): the reference's caller code imports ``model.*`` / ``pcdet.*`` (train_func.py:20-34); after install()
 those names must resolve to this package, the reference's own YAML (Multimodal_cfg/mil3.yaml) must load through the
 mirrored ``cfg_from_yaml_file`` and ``GAR_Fusion_ALL(cfg, dataset)`` must build from it with the reference's parameter
-names.  Runs in a child process (install() edits sys.modules / sys.meta_path)."""
+names.  The YAML is a verbatim copy of the reference's file, stored as tests/golden/mil3.yaml.  Runs in a child process
+(install() edits sys.modules / sys.meta_path)."""
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MIL3 = "/root/reference/Multimodal_cfg/mil3.yaml"
+MIL3 = os.path.join(ROOT, "tests", "golden", "mil3.yaml")
 
 CHILD = r"""
 import sys
@@ -100,7 +99,6 @@ def test_compat_install_aliases_reference_import_names():
     _run("")
 
 
-@pytest.mark.skipif(not os.path.exists(MIL3), reason="the reference tree (and its mil3.yaml) exists in the build container only")
 def test_compat_install_builds_gar_fusion_all_from_reference_yaml():
     out = _run(MIL3)
     assert "built GAR_Fusion_ALL from mil3.yaml" in out and "built JRDB_act from mil3.yaml" in out

@@ -1,43 +1,41 @@
 """Per-actor point crop: the oracle's box test is PINNED against the reference's own CPU
-implementation -- points_in_boxes_cpu of /root/reference/pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:118-168, built
-from that file where it lies by oracle/build_ref.sh into oracle/_ref/ (git-ignored; build container only) -- on points
+implementation -- points_in_boxes_cpu of the reference's pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:118-168, whose
+decisions are stored in tests/golden/reference_points_in_boxes.npz (it is built from the reference's file by
+oracle/build_ref.sh into the git-ignored oracle/_ref/ where that tree is present, and then run as well) -- on points
 crowded around the box faces, where every rounding choice of the test (float vs double compares, cos / sin of the negated
 heading, un-contracted products) shows.  The two differ only in MARGIN (1e-2 in the CPU function, 1e-5 in the CUDA
 kernels roiaware_pool3d_kernel.cu:27 / roipoint_pool3d_kernel.cu:27), which the oracle takes as a parameter."""
+import hashlib
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "golden"))
+from point_crop_cases import CASE, boundary_cases  # noqa: E402
 
-def _boundary_cases(seed, n_boxes, n_pts):
-    rng = np.random.default_rng(seed)
-    boxes = np.concatenate([rng.uniform(-10, 10, (n_boxes, 2)), rng.uniform(-1, 1, (n_boxes, 1)), rng.uniform(0.4, 3.0, (n_boxes, 3)),
-                            rng.uniform(-np.pi, np.pi, (n_boxes, 1))], 1).astype(np.float32)
-    pts = []
-    for b in boxes:
-        # points in the box frame, most of them within 1e-7 .. 5e-2 of a face, then rotated into the world frame
-        u = rng.uniform(-1, 1, (n_pts // n_boxes, 3))
-        face = rng.integers(0, 3, len(u))
-        sign = rng.choice([-1.0, 1.0], len(u))
-        eps = sign * 10.0 ** rng.uniform(-7, -0.5, len(u)) * rng.choice([-1.0, 1.0], len(u))
-        u[np.arange(len(u)), face] = sign + eps
-        loc = u * (b[3:6].astype(np.float64) / 2)
-        c, s = np.cos(b[6]), np.sin(b[6])
-        world = np.stack([loc[:, 0] * c - loc[:, 1] * s + b[0], loc[:, 0] * s + loc[:, 1] * c + b[1], loc[:, 2] + b[2]], 1)
-        pts.append(world)
-    return boxes, np.concatenate(pts).astype(np.float32)
+GOLD = os.path.join(HERE, "golden", "reference_points_in_boxes.npz")
 
 
 def test_oracle_box_test_equals_the_reference_cpu_build(oracle):
+    """Against the decisions of the reference's points_in_boxes_cpu stored in tests/golden/reference_points_in_boxes.npz
+    (make_reference_points_in_boxes_golden.py); where oracle/_ref holds the reference's build it is run as well."""
+    g = np.load(GOLD)
+    boxes, pts = boundary_cases(*CASE)
+    assert np.array_equal(boxes, g["boxes"]) and hashlib.sha256(pts.tobytes()).hexdigest() == str(g["pts_sha256"]), \
+        "the seeded boundary case no longer reproduces the fixture's inputs"
+    want = np.unpackbits(g["mask_bits"], axis=1, count=int(g["n_pts"])).astype(np.int32)
     ref = oracle.load_reference_roiaware()
-    if ref is None:
-        pytest.skip("oracle/_ref is built in the build container only (oracle/build_ref.sh needs /root/reference)")
-    boxes, pts = _boundary_cases(1, 24, 48000)
-    want = torch.zeros((boxes.shape[0], pts.shape[0]), dtype=torch.int32)
-    ref.points_in_boxes_cpu(torch.from_numpy(boxes), torch.from_numpy(pts), want)
+    if ref is not None:
+        live = torch.zeros((boxes.shape[0], pts.shape[0]), dtype=torch.int32)
+        ref.points_in_boxes_cpu(torch.from_numpy(boxes), torch.from_numpy(pts), live)
+        assert np.array_equal(live.numpy(), want), "the reference's build disagrees with the stored fixture"
     got = oracle.points_in_boxes_mask(boxes, pts, 1e-2)
-    assert np.array_equal(got, want.numpy()), "%d of %d decisions differ" % ((got != want.numpy()).sum(), got.size)
-    inside = want.numpy().sum()
+    assert np.array_equal(got, want), "%d of %d decisions differ" % ((got != want).sum(), got.size)
+    inside = want.sum()
     assert 0.2 * pts.shape[0] < inside < 0.95 * pts.shape[0]          # the cases straddle the faces
     # the margin matters on these points: the CUDA kernels' 1e-5 gives a different answer for thousands of them
     assert (oracle.points_in_boxes_mask(boxes, pts, 1e-5) != got).sum() > 1000

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_point_crop_cpu import _boundary_cases
+from test_point_crop_cpu import boundary_cases as _boundary_cases  # tests/golden/point_crop_cases.py
 
 pytestmark = pytest.mark.gpu
 

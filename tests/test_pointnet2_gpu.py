@@ -427,6 +427,71 @@ def test_fused_query_group_batch_equals_op_chain(ops):
     assert torch.equal(qg(xyz, new_xyz, None), rel)  # xyz-only grouping
 
 
+def _qg_backward(pb, xyz, new_xyz, feats, radius, nsample, g):
+    feats.grad = None
+    pb.QueryAndGroup(radius, nsample, use_xyz=True)(xyz, new_xyz, feats).backward(g)
+    torch.cuda.synchronize()
+    return feats.grad.clone()
+
+
+# (n, queries, nsample): one LDS window with 16-byte loads; two windows of the int64 row; cols % 4 != 0 (the scalar path,
+# and the gradient rows then start off 16-byte boundaries)
+@pytest.mark.parametrize("n,npoint,nsample", [(4096, 512, 32), (20000, 2500, 32), (3001, 375, 5)])
+def test_query_group_batch_backward_is_reproducible_and_exact(ops, n, npoint, nsample):
+    """The batch grouping backward adds in order-free fixed point: two runs give the same bits, and every cell is the
+    float64 scatter-add within one fp32 rounding plus the kernel's fixed-point bound (csrc/query_group.hip,
+    qg_batch_bwd_lds_kernel): k contributions, each rounded by at most max|g of the row| * cols * 2^-61."""
+    pb = ops[0]
+    rng = np.random.default_rng(5)
+    xyz = dev(scene_xyz(8, 2, n))
+    new_xyz = xyz[:, :npoint].contiguous()
+    feats = dev(rng.standard_normal((2, 6, n)).astype(np.float32)).requires_grad_(True)
+    out = pb.QueryAndGroup(2.0, nsample, use_xyz=True)(xyz, new_xyz, feats)
+    shape = tuple(out.shape)
+    g = dev((rng.standard_normal(shape) * 10.0 ** rng.uniform(-3, 3, shape)).astype(np.float32))
+    got = _qg_backward(pb, xyz, new_xyz, feats, 2.0, nsample, g)
+    assert torch.equal(got, _qg_backward(pb, xyz, new_xyz, feats, 2.0, nsample, g))
+    idx = pb.ball_query(2.0, nsample, xyz, new_xyz).cpu().numpy().reshape(2, -1)
+    cols = idx.shape[1]
+    assert (cols % 4 != 0) == (nsample == 5)
+    gf = g[:, 3:].double().cpu().numpy().reshape(2, 6, cols)
+    want = np.zeros((2, 6, n))
+    for b in range(2):
+        for c in range(6):
+            np.add.at(want[b, c], idx[b], gf[b, c])
+    k = np.stack([np.bincount(idx[b], minlength=n) for b in range(2)])[:, None, :]          # contributions per cell
+    assert k.max() > 8
+    row_max = np.abs(gf).max(axis=2, keepdims=True)
+    bound = np.spacing(np.abs(want).astype(np.float32)).astype(np.float64) + k * row_max * cols * 2.0 ** -61 \
+        + k * row_max * 2.0 ** -50                                                            # + the float64 reference's own
+    err = np.abs(got.double().cpu().numpy() - want)
+    assert (err <= bound).all(), "worst cell: err %g, bound %g" % (err.max(), bound[err > bound].min())
+
+
+def test_query_group_batch_backward_propagates_non_finite_gradients(ops):
+    """A NaN or an inf anywhere in a gradient row reaches the cells its columns point at (the float path of the kernel), and
+    the other rows keep their finite, unchanged values."""
+    pb = ops[0]
+    rng = np.random.default_rng(6)
+    n, npoint, nsample = 4096, 512, 32
+    xyz = dev(scene_xyz(9, 2, n))
+    new_xyz = xyz[:, :npoint].contiguous()
+    feats = dev(rng.standard_normal((2, 6, n)).astype(np.float32)).requires_grad_(True)
+    out = pb.QueryAndGroup(2.0, nsample, use_xyz=True)(xyz, new_xyz, feats)
+    g = dev(rng.standard_normal(tuple(out.shape)).astype(np.float32))
+    clean = _qg_backward(pb, xyz, new_xyz, feats, 2.0, nsample, g)
+    idx = pb.ball_query(2.0, nsample, xyz, new_xyz).cpu().numpy()
+    g_bad = g.clone()
+    g_bad[0, 3 + 1, 400, 30] = float("nan")                  # late in row (0, 1): after many finite elements of that thread
+    g_bad[1, 3 + 2, 7, 2] = float("inf")
+    got = _qg_backward(pb, xyz, new_xyz, feats, 2.0, nsample, g_bad).cpu().numpy()
+    assert np.isnan(got[0, 1, idx[0, 400, 30]])
+    assert got[1, 2, idx[1, 7, 2]] == np.inf
+    keep = np.ones((2, 6), bool)
+    keep[0, 1] = keep[1, 2] = False
+    assert np.isfinite(got[keep]).all() and np.array_equal(got[keep], clean.cpu().numpy()[keep])
+
+
 def test_fused_query_group_stack_equals_op_chain(ops):
     ps = ops[1]
     rng = np.random.default_rng(13)
