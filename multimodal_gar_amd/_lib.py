@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmgar_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -110,7 +110,6 @@ _PROTOS = {
     "mgar_stem_conv3d_workspace_floats": [],
     "mgar_stem_conv3d_set_minimal_filtering": [_I],
     "mgar_stem_conv3d_fwd": [_P, _I, _I, _I, _I, _P, _P, _P, _P],
-    "mgar_delay_us": [_I, _P],
     "mgar_conv3d_k3_workspace_floats": [_I, _I],
     "mgar_conv3d_k3_set_lds_pad": [_I],
     "mgar_conv3d_k3_fwd": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],

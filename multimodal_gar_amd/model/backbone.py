@@ -166,12 +166,9 @@ class Unit3D(nn.Module):
             c = self.conv3d
             w2 = c.weight.view(c.out_channels, c.in_channels)
             x3 = x.flatten(2)
-            if os.environ.get("MGAR_1X1_MODE", "mm_loop") == "bmm":          # diagnostics: the batched call
-                y = torch.bmm(w2.unsqueeze(0).expand(x3.shape[0], -1, -1), x3)
-            else:
-                y = torch.empty((x3.shape[0], c.out_channels, x3.shape[2]), dtype=x.dtype, device=x.device)
-                for n in range(x3.shape[0]):
-                    torch.mm(w2, x3[n], out=y[n])
+            y = torch.empty((x3.shape[0], c.out_channels, x3.shape[2]), dtype=x.dtype, device=x.device)
+            for n in range(x3.shape[0]):
+                torch.mm(w2, x3[n], out=y[n])
             if c.bias is not None:
                 y = y + c.bias.view(1, -1, 1)
             return y.view(x.shape[0], c.out_channels, *x.shape[2:])

@@ -136,33 +136,26 @@ class ClipModel(nn.Module):
         # pooling kernels +3.5 ms in that layout, step 229.4 -> ~226 ms -- but MIOpen's search over its NDHWC kernel
         # instances takes 4 min 20 s at start-up on a fresh box (NCDHW: 35-40 s), shipped find-db or not, so it is off.
         self.i3d_channels_last = False
-        self._side_stream = self._geo_stream = None
-        # What of the trunk's coordinate-only work is issued ahead of the feature path: "fps1" = the level-1 FPS, on the main
-        # stream before the I3D launches (round 1); "all" = every level's FPS, ball queries and 3-NN weights on a third
-        # stream.  "all" measured SLOWER inside the HIP graph (1 clip: 45.4 vs 42.3 ms; c3: 244.2 vs 235.2 ms/step,
-        # profiles/README.md round 2): the extra branch delays the feature path's kernels more than it hides.
-        self.geometry_ahead = "fps1"
+        # Side streams of the forked and pipelined schedules, created by _make_streams
+        self._rgb_stream = None         # the frozen I3D + RoIAlign pass (forked: the trainable RGB tail too)
+        self._lidar_stream = None       # forked: the LiDAR branch, forward and hence backward
+        self._geometry_stream = None    # the trunk's coordinate-only chain (forked: this batch's; pipelined: the next batch's)
         # Opt-in (bench.py --prefetch-geometry): input-side software pipelining.  The trunk's coordinate-only work (FPS of all
         # levels, ball queries, 3-NN weights) depends on the points alone, so a step can compute it for the NEXT batch on a side
         # stream while it runs the feature path and the backward of the current one -- as a loader would.  Every step still does
         # the geometry of one batch and the forward + backward of one batch; only the order changes.  It takes the level-1 FPS
-        # (4.6 ms on 15 workgroups at one clip per rank) off the critical path.  Off by default: the headline numbers are the
-        # un-pipelined step.
+        # (4.6 ms on 15 workgroups at one clip per rank) off the critical path.  Off by default: the headline is the plain step.
         self.geometry_prefetch = False
-        self.geometry_stream_max_clouds = int(os.environ.get("MGAR_GEOMETRY_STREAM_MAX_CLOUDS", 60))   # see forward()
-        # Two-stream step: the LiDAR branch on a third stream instead of the issuing one (see forward())
-        self.branches_off_origin = os.environ.get("MGAR_BRANCHES_OFF_ORIGIN", "1") != "0"
-        # Microseconds by which the RGB side stream starts after the level-1 FPS kernel has gone out (see forward()); 0 = off
-        self.sampling_head_start_us = int(os.environ.get("MGAR_SAMPLING_HEAD_START_US", 20))
+        self.geometry_stream_max_clouds = int(os.environ.get("MGAR_GEOMETRY_STREAM_MAX_CLOUDS", 60))   # see _forward_forked()
         # Opt-in (bench.py --prefetch-rgb): the same pipelining for the FROZEN RGB branch.  I3D + RoIAlign carry no gradient and
         # depend on the frames alone, so a step can run them for the NEXT batch on the side stream under its own BACKWARD (an
         # MFMA-bound pass beside streaming kernels) instead of beside the LiDAR forward.  Every step still runs one I3D pass; only
         # the order across the step boundary changes.  Off by default, like geometry_prefetch.
         self.rgb_prefetch = False
         self._rgb_cur = None        # RoI crops of the batch this step consumes
-        self._rgb_next = None       # crops being computed for the next step (owned by the side stream until finish_prefetch)
+        self._rgb_next = None       # crops being computed for the next step (owned by the RGB stream until finish_prefetch)
         self._geo_cur = None        # geometry of the batch this step consumes (computed during the previous step)
-        self._geo_next = None       # geometry being computed for the next step (owned by the side stream until finish_prefetch)
+        self._geo_next = None       # geometry being computed for the next step (owned by the geometry stream until finish_prefetch)
 
     # ---- RGB: one I3D pass per clip (batch 1, like the reference) ---------------------------------
     def rgb_crops(self, images, bboxes):
@@ -208,16 +201,15 @@ class ClipModel(nn.Module):
         return self.rgb_tokens_from_crops(self.rgb_crops(images, bboxes))
 
     # ---- LiDAR: all frames of all clips in one batch ------------------------------------------------
-    def trunk_geometry(self, points, stream=None):
-        """The coordinate-only part of the PointNet++ trunk (FPS centres of the four levels, ball queries of the folded
-        scales, 3-NN weights of the decoder), issued ahead of the feature path on ``stream``: level-1 FPS runs one workgroup
-        per cloud for ~5 ms (6-47 % of the CUs) and overlaps the I3D work (see ``geometry_ahead``)."""
+    def trunk_geometry(self, points, stream, whole_chain):
+        """The coordinate-only part of the PointNet++ trunk issued ahead of the feature path on ``stream``: with
+        ``whole_chain`` the FPS centres of the four levels, the ball queries of the folded scales and the 3-NN weights of the
+        decoder; without it the level-1 FPS alone (one workgroup per cloud for ~5 ms, 6-47 % of the CUs), and the SA / FP
+        modules compute the rest in line."""
         if self.route != "pointnet2":
             return None
-        trunk = self.net.LiDAR_backbone.model.backbone_3d
-        if self.geometry_ahead == "all":
-            return trunk.geometry(points, stream)
-        return trunk.geometry(points, stream, levels=1, balls=False, neighbours=False)
+        only_fps1 = {} if whole_chain else dict(levels=1, balls=False, neighbours=False)
+        return self.net.LiDAR_backbone.model.backbone_3d.geometry(points, stream, **only_fps1)
 
     def lidar_tokens(self, points, bboxes3d, geometry=None):
         f, p, _ = points.shape
@@ -237,126 +229,126 @@ class ClipModel(nn.Module):
         return tok.view(f, a, -1)
 
     def finish_prefetch(self):
-        """After the step's BACKWARD (its saved index tensors are the current geometry): join the side stream that computed
-        the next batch's geometry and make it the current one -- by copying into the current buffers, so that a captured HIP
-        graph keeps reading the same addresses."""
+        """Pipelined schedule, after the step's BACKWARD (its saved index tensors are the current geometry): join the streams
+        that computed the next batch's RoI crops and geometry and make those the current ones -- by copying into the current
+        buffers, so that a captured HIP graph keeps reading the same addresses."""
         if self._rgb_next is not None:
-            main = torch.cuda.current_stream()
-            main.wait_stream(self._side_stream)
-            capturing = torch.cuda.is_current_stream_capturing()
-            for a_, b_ in zip(self._rgb_cur, self._rgb_next):
-                if not capturing:
-                    b_.record_stream(main)
-                a_.copy_(b_)
-            self._rgb_next = None
-        if self._geo_next is None:
-            return
-        main = torch.cuda.current_stream()
-        main.wait_stream(self._geo_stream)
-        src, dst = _geometry_tensors(self._geo_next), _geometry_tensors(self._geo_cur)
-        assert len(src) == len(dst)
-        capturing = torch.cuda.is_current_stream_capturing()
-        for a_, b_ in zip(dst, src):
-            if not capturing:
-                b_.record_stream(main)
-            a_.copy_(b_)
-        self._geo_next = None
+            _adopt(self._rgb_stream, self._rgb_cur, self._rgb_next)
+        if self._geo_next is not None:
+            _adopt(self._geometry_stream, _geometry_tensors(self._geo_cur), _geometry_tensors(self._geo_next))
+        self._rgb_next = self._geo_next = None
+
+    def _make_streams(self, lidar=False, geometry=False):
+        """The one place the side streams come from: each is created when a schedule first needs it."""
+        if self._rgb_stream is None:
+            self._rgb_stream = torch.cuda.Stream()
+        if lidar and self._lidar_stream is None:
+            self._lidar_stream = torch.cuda.Stream()
+        if geometry and self._geometry_stream is None:
+            self._geometry_stream = torch.cuda.Stream()
 
     def forward(self, batch):
-        b, t, a = batch["n_clips"], batch["n_frames"], self.n_actors
-        if batch["images"].is_cuda and self.overlap_branches:
-            # The frozen I3D pass (MFMA-heavy convolutions, no autograd graph) runs on a side HIP stream next to the
-            # LiDAR branch on the main stream.  Issue order: level-1 FPS first (a single launch that leaves most of
-            # the chip idle), then the I3D launches, then the rest of the LiDAR branch.  Nothing that autograd will
-            # replay lives on the side stream, so gradient hooks (DDP) only ever see the main stream.
-            main = torch.cuda.current_stream()
-            if self._side_stream is None:
-                self._side_stream, self._geo_stream = torch.cuda.Stream(), torch.cuda.Stream()
-            inputs_ready = main.record_event()
-            self._geo_stream.wait_event(inputs_ready)
-            prefetch = self.geometry_prefetch and self.route == "pointnet2"
-            if prefetch:
-                trunk = self.net.LiDAR_backbone.model.backbone_3d
-                if self._geo_cur is None:      # first step: nothing was prefetched -- compute it in line, once
-                    self._geo_cur = _without_events(trunk.geometry(batch["points"]))
-                geometry = self._geo_cur
-                # the NEXT batch's geometry (the caller passes its points; the benchmark's batches are all the same tensor)
-                self._geo_next = trunk.geometry(batch.get("next_points", batch["points"]), self._geo_stream)
-            else:
-                geometry = None
-            from . import _lib as L
-            from .pcdet.ops.pointnet2.pointnet2_batch import pointnet2_batch_cuda as shim
-            sampling_goes_out = []
-            if not prefetch and self.sampling_head_start_us > 0:
-                # The level-1 FPS (one 1024-thread workgroup per cloud, the head of the LiDAR chain) has to be RESIDENT before the
-                # I3D stem's workgroups start streaming through the CUs, or it starts when the stem ends (csrc/errors.hip,
-                # mgar_delay_us): the side stream waits for the moment the sampling kernel goes out, plus a few microseconds.
-                shim.BEFORE_SAMPLING_LAUNCH = lambda: sampling_goes_out.append(torch.cuda.current_stream().record_event())
-            try:
-                if not prefetch and not (self.branches_off_origin and not self.rgb_prefetch):
-                    geometry = self.trunk_geometry(batch["points"], self._geo_stream if self.geometry_ahead == "all" else main)   # FPS first
-            finally:
-                shim.BEFORE_SAMPLING_LAUNCH = None
-            self._side_stream.wait_event(inputs_ready)
-            if self.branches_off_origin and not self.rgb_prefetch and not prefetch:
-                # Both branches away from the stream the step is issued (and captured) on: the RGB branch on the side stream, the
-                # LiDAR branch -- forward here, hence its backward too -- on a third one; the issuing stream only forks and joins.
-                # Measured against the LiDAR branch on the issuing stream (same box, 3 runs each): 177.6-178.4 vs 182.1-182.6 ms
-                # at 8 clips, 95.6 vs 96.9 at 4, 54.2 vs 55.2 at 2, 34.4 both at 1.
-                lst = self._geo_stream
-                with torch.cuda.stream(self._side_stream):     # (issued first: with the LiDAR branch first -- and the RGB branch
-                    crops = self.rgb_crops(batch["images"], batch["bboxes"])   # held back until its sampling kernel is out -- 179.5 ms)
-                    # the trainable RGB tail (non-local block, embedding, GAT) too: its forward beside the LiDAR forward, its
-                    # backward beside the LiDAR backward (8 clips 176.3 -> 175.6 ms, 1 clip 32.9 -> 32.5)
-                    rgb = self.rgb_tokens_from_crops(crops)
-                geo = None
-                if self.route == "pointnet2" and batch["points"].shape[0] <= self.geometry_stream_max_clouds:
-                    # few clouds: the trunk's coordinate-only chain (FPS of the four levels, ball queries, 3-NN weights -- every
-                    # level's FPS waits for the previous one and occupies one workgroup per cloud) on a stream of its own, ahead of
-                    # the feature path.  Same box: 33.1 vs 34.1 ms at 1 clip (15 clouds), 53.2 vs 54.1 at 2, 95.1 vs 95.7 at 4;
-                    # 178.3 vs 177.5 at 8 (120 clouds: off).
-                    if getattr(self, "_geo4_stream", None) is None:
-                        self._geo4_stream = torch.cuda.Stream()
-                    self._geo4_stream.wait_event(inputs_ready)
-                    ga, self.geometry_ahead = self.geometry_ahead, "all"
-                    try:
-                        geo = self.trunk_geometry(batch["points"], self._geo4_stream)
-                    finally:
-                        self.geometry_ahead = ga
-                with torch.cuda.stream(lst):
-                    lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"], geo)
-                if geo is not None:
-                    main.wait_stream(self._geo4_stream)
-                main.wait_stream(self._side_stream)
-                main.wait_stream(lst)
-                if not torch.cuda.is_current_stream_capturing():
-                    for c in crops:
-                        c.record_stream(main)
-                    lidar.record_stream(main)
-                    rgb.record_stream(main)
-                return self._fuse(batch, rgb, lidar)
-            if self.rgb_prefetch:
-                if self._rgb_cur is None:      # first step: nothing was prefetched -- compute it in line, once
-                    self._rgb_cur = [c.clone() for c in self.rgb_crops(batch["images"], batch["bboxes"])]
-                crops = self._rgb_cur
-            else:
-                if sampling_goes_out:
-                    self._side_stream.wait_event(sampling_goes_out[0])
-                    L.call("mgar_delay_us", int(self.sampling_head_start_us), self._side_stream.cuda_stream)
-                with torch.cuda.stream(self._side_stream):
-                    crops = self.rgb_crops(batch["images"], batch["bboxes"])
-            lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"], geometry)   # (B*T, A, 512)
-            main.wait_stream(self._side_stream)
-            if not prefetch:
-                main.wait_stream(self._geo_stream)
+        """Picks one of three stream schedules; each joins its side streams into the issuing stream before the fusion net."""
+        if not (batch["images"].is_cuda and self.overlap_branches):
+            return self._forward_serial(batch)
+        if (self.geometry_prefetch and self.route == "pointnet2") or self.rgb_prefetch:
+            return self._forward_pipelined(batch)
+        return self._forward_forked(batch)
+
+    def _forward_serial(self, batch):
+        """Everything on the current stream, in order: RGB branch, LiDAR branch, fusion net."""
+        rgb = self.rgb_tokens(batch["images"], batch["bboxes"])                   # (B, A, 512)
+        lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"])             # (B*T, A, 512)
+        return self._fuse(batch, rgb, lidar)
+
+    def _forward_forked(self, batch):
+        """Both branches away from the stream the step is issued (and captured) on, which only forks and joins:
+
+          issuing stream : records ``inputs_ready``; ... waits for geometry, RGB, LiDAR stream (in that order); fusion net
+          RGB stream     : waits for inputs_ready; frozen I3D + RoIAlign, then the trainable RGB tail        (issued first)
+          geometry stream: waits for inputs_ready; the trunk's whole coordinate-only chain                  (issued second;
+                           PointNet++ route with at most ``geometry_stream_max_clouds`` clouds only)
+          LiDAR stream   : waits for inputs_ready; the LiDAR branch, whose SA / FP modules wait for the geometry stream's
+                           per-level events where that stream is in use and compute the geometry in line otherwise
+
+        The backward of each branch runs on the stream of its forward.  The measurements behind the issue order, the RGB tail
+        on the RGB stream and the 60-cloud limit of the geometry stream: DESIGN.md section 4a."""
+        points = batch["points"]
+        use_geometry_stream = self.route == "pointnet2" and points.shape[0] <= self.geometry_stream_max_clouds
+        self._make_streams(lidar=True, geometry=use_geometry_stream)
+        main = torch.cuda.current_stream()
+        inputs_ready = main.record_event()
+        self._rgb_stream.wait_event(inputs_ready)
+        with torch.cuda.stream(self._rgb_stream):
+            crops = self.rgb_crops(batch["images"], batch["bboxes"])
+            rgb = self.rgb_tokens_from_crops(crops)
+        geometry = None
+        if use_geometry_stream:
+            self._geometry_stream.wait_event(inputs_ready)
+            geometry = self.trunk_geometry(points, self._geometry_stream, whole_chain=True)
+        self._lidar_stream.wait_event(inputs_ready)
+        with torch.cuda.stream(self._lidar_stream):
+            lidar = self.lidar_tokens(points, batch["bboxes3d"], geometry)
+        if use_geometry_stream:
+            main.wait_stream(self._geometry_stream)
+        main.wait_stream(self._rgb_stream)
+        main.wait_stream(self._lidar_stream)
+        if not torch.cuda.is_current_stream_capturing():   # inside a graph the pool is private and replays are serial
+            for c in crops:
+                c.record_stream(main)
+            lidar.record_stream(main)
+            rgb.record_stream(main)
+        return self._fuse(batch, rgb, lidar)
+
+    def _forward_pipelined(self, batch):
+        """Input-side software pipelining (``geometry_prefetch`` and / or ``rgb_prefetch``): the LiDAR branch, the trainable
+        RGB tail and the fusion net on the issuing stream, the input-only work of the NEXT batch on side streams.
+
+          issuing stream : records ``inputs_ready``; [first step only: what was not prefetched, in line]; without
+                           geometry_prefetch the level-1 FPS ahead of everything else (a single launch that leaves most of the
+                           chip idle); LiDAR branch; waits for the RGB stream (without rgb_prefetch); RGB tail; fusion net
+          geometry stream: (geometry_prefetch) waits for inputs_ready; the whole coordinate-only chain of the next batch
+          RGB stream     : without rgb_prefetch: waits for inputs_ready; this batch's frozen I3D + RoIAlign
+                           with rgb_prefetch: waits for the end of the forward; the next batch's frozen pass,
+                           which then runs under this step's objective and backward
+
+        ``finish_prefetch`` joins what ran for the next batch, after the backward."""
+        geometry_prefetch = self.geometry_prefetch and self.route == "pointnet2"
+        self._make_streams(geometry=geometry_prefetch)
+        main = torch.cuda.current_stream()
+        inputs_ready = main.record_event()
+        if geometry_prefetch:
+            if self._geo_cur is None:      # first step: nothing was prefetched -- compute it in line, once
+                self._geo_cur = _without_events(self.trunk_geometry(batch["points"], main, whole_chain=True))
+            geometry = self._geo_cur
+            # the NEXT batch's geometry (the caller passes its points; the benchmark's batches are all the same tensor)
+            self._geometry_stream.wait_event(inputs_ready)
+            self._geo_next = self.trunk_geometry(batch.get("next_points", batch["points"]), self._geometry_stream, whole_chain=True)
+        else:
+            geometry = self.trunk_geometry(batch["points"], main, whole_chain=False)
+        if self.rgb_prefetch:
+            if self._rgb_cur is None:      # first step: nothing was prefetched -- compute it in line, once
+                self._rgb_cur = [c.clone() for c in self.rgb_crops(batch["images"], batch["bboxes"])]
+            crops = self._rgb_cur
+        else:
+            self._rgb_stream.wait_event(inputs_ready)
+            with torch.cuda.stream(self._rgb_stream):
+                crops = self.rgb_crops(batch["images"], batch["bboxes"])
+        lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"], geometry)   # (B*T, A, 512)
+        if not self.rgb_prefetch:
+            main.wait_stream(self._rgb_stream)
             if not torch.cuda.is_current_stream_capturing():   # inside a graph the pool is private and replays are serial
                 for c in crops:
                     c.record_stream(main)
-            rgb = self.rgb_tokens_from_crops(crops)                                   # (B, A, 512)
-        else:
-            rgb = self.rgb_tokens(batch["images"], batch["bboxes"])
-            lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"])
-        return self._fuse(batch, rgb, lidar)
+        rgb = self.rgb_tokens_from_crops(crops)                                   # (B, A, 512)
+        out = self._fuse(batch, rgb, lidar)
+        if self.rgb_prefetch:
+            # the NEXT batch's frozen RGB pass (the caller passes its frames; the benchmark's batches are all the same tensor),
+            # issued where the forward ends
+            self._rgb_stream.wait_event(main.record_event())
+            with torch.cuda.stream(self._rgb_stream):
+                self._rgb_next = self.rgb_crops(batch.get("next_images", batch["images"]), batch.get("next_bboxes", batch["bboxes"]))
+        return out
 
     def _fuse(self, batch, rgb, lidar):
         b, t, a = batch["n_clips"], batch["n_frames"], self.n_actors
@@ -366,15 +358,19 @@ class ClipModel(nn.Module):
         # The fusion net works on (A, 512) tokens per scene: launch-bound, not bandwidth-bound.  It runs in fp32 on every
         # configuration (under the bf16 configurations the token producers above are bf16; the tokens are widened here).
         with torch.autocast(device_type=rgb_s.device.type, enabled=False):
-            out = self.net.GAR_model(pad(rgb_s.float()), pad(lidar.float()), bb2, batch["bboxes3d"], None, batch["person_id"])
-        if batch["images"].is_cuda and self.overlap_branches and self.rgb_prefetch:
-            # the NEXT batch's frozen RGB pass (the caller passes its frames; the benchmark's batches are all the same tensor),
-            # issued where the forward ends: it runs on the side stream under this step's objective and backward
-            main = torch.cuda.current_stream()
-            self._side_stream.wait_event(main.record_event())
-            with torch.cuda.stream(self._side_stream):
-                self._rgb_next = self.rgb_crops(batch.get("next_images", batch["images"]), batch.get("next_bboxes", batch["bboxes"]))
-        return out
+            return self.net.GAR_model(pad(rgb_s.float()), pad(lidar.float()), bb2, batch["bboxes3d"], None, batch["person_id"])
+
+
+def _adopt(stream, current, prefetched):
+    """Join ``stream`` into the current one and copy the tensors it produced over the current ones."""
+    main = torch.cuda.current_stream()
+    main.wait_stream(stream)
+    assert len(current) == len(prefetched)
+    capturing = torch.cuda.is_current_stream_capturing()
+    for cur, nxt in zip(current, prefetched):
+        if not capturing:
+            nxt.record_stream(main)
+        cur.copy_(nxt)
 
 
 def _geometry_tensors(geo):
@@ -429,7 +425,41 @@ def reference_loss(outputs, batch):
                                       batch["n_actors"], Loss="L_total", reference_semantics=False)["L_total"]
 
 
-class TrainStep:
+class _GraphStep:
+    """What TrainStep and ForwardStep share: warm-up, capture into a HIP graph (torch.cuda.CUDAGraph) and replay on a static
+    batch.  A subclass provides ``run_eager(batch)`` and decides what it records."""
+    graph = None
+    _static_batch = None
+
+    def _warm_up(self, batch, warmup):
+        """``batch``'s tensors become the static inputs (later batches are copied into them); `warmup` eager steps run
+        first on a side stream, as graph capture requires."""
+        assert self.graph is None and batch["images"].is_cuda
+        self._static_batch = batch
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self.run_eager(batch)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+
+    def _record(self, fn):
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = fn()
+        self.graph = graph
+        return out
+
+    def _replay(self, batch):
+        if batch is not self._static_batch:
+            for k, v in batch.items():
+                if torch.is_tensor(v):
+                    self._static_batch[k].copy_(v)
+        self.graph.replay()
+
+
+class TrainStep(_GraphStep):
     """model + Adam + data parallelism; ``run(batch)`` = forward, loss, backward, (gradient all-reduce,) optimizer step.
 
     ddp=True wraps the model in DistributedDataParallel (bucketed all-reduce overlapped with backward).
@@ -465,8 +495,6 @@ class TrainStep:
         self.params = [p for p in self.model.parameters() if p.requires_grad]
         # train_func.py:552 Adam(lr=1e-3); on the device the fused implementation (a handful of launches instead of ~30)
         self.opt = torch.optim.Adam(self.params, lr=lr, fused=(device.type == "cuda") or None)
-        self.graph = None
-        self._static_batch = None
         self._loss = None
 
     # ---- eager step ------------------------------------------------------------------------------
@@ -528,37 +556,24 @@ class TrainStep:
 
     # ---- HIP-graph step ---------------------------------------------------------------------------
     def capture(self, batch, warmup=2):
-        """Record forward + backward on ``batch`` (its tensors become the static inputs: later batches are copied
-        into them).  `warmup` eager steps run first on a side stream, as graph capture requires."""
-        assert self.graph is None and batch["images"].is_cuda
+        """Record forward + backward on ``batch``, after `warmup` eager steps."""
         assert not hasattr(self.model, "module") or self.model is self.module, "capture() needs manual_allreduce, not DDP"
-        self._static_batch = batch
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self.run_eager(batch)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        self._warm_up(batch, warmup)
         self.opt.zero_grad(set_to_none=True)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self.model(batch)
-            loss = self._loss_of(out, batch)
+
+        def forward_backward():
+            loss = self._loss_of(self.model(batch), batch)
             loss.backward()
             self.module.finish_prefetch()
-        self.graph, self._loss = graph, loss.detach()
+            return loss.detach()
+        self._loss = self._record(forward_backward)
         self._graph_grads = [p.grad for p in self.params]   # the buffers every replay writes (graph-private pool)
         return self
 
     def run(self, batch):
         if self.graph is None:
             return self.run_eager(batch)
-        if batch is not self._static_batch:
-            for k, v in batch.items():
-                if torch.is_tensor(v):
-                    self._static_batch[k].copy_(v)
-        self.graph.replay()
+        self._replay(batch)
         for p, g in zip(self.params, self._graph_grads):      # an eager step in between re-points .grad elsewhere
             p.grad = g
         self._exchange_gradients()
@@ -566,7 +581,7 @@ class TrainStep:
         return self._loss
 
 
-class ForwardStep:
+class ForwardStep(_GraphStep):
     """Train-mode forward of the clip model (batch-statistics BatchNorm, dropout active) without autograd: the workload of
     BASELINE configs c2 / c5.  precision="bf16": feature payloads and GEMMs / convolutions in bf16 -- the hand-written
     kernels take bf16 payloads directly (include/mgar_ops.h, `_bf16` entry points: fp32 arithmetic inside, fp32 BatchNorm
@@ -588,8 +603,6 @@ class ForwardStep:
             for m in self.model.net.RGB_backbone.backbone_net.modules():
                 if isinstance(m, nn.Conv3d):
                     m.weight.data = m.weight.data.to(torch.bfloat16)
-        self.graph = None
-        self._static_batch = None
         self._out = None
 
     def _forward(self, batch):
@@ -600,29 +613,14 @@ class ForwardStep:
         return self._forward(batch)
 
     def capture(self, batch, warmup=2):
-        assert self.graph is None and batch["images"].is_cuda
-        self._static_batch = batch
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._forward(batch)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self._forward(batch)
-        self.graph, self._out = graph, out
+        self._warm_up(batch, warmup)
+        self._out = self._record(lambda: self._forward(batch))
         return self
 
     def run(self, batch):
         if self.graph is None:
             return self._forward(batch)
-        if batch is not self._static_batch:
-            for k, v in batch.items():
-                if torch.is_tensor(v):
-                    self._static_batch[k].copy_(v)
-        self.graph.replay()
+        self._replay(batch)
         return self._out
 
 

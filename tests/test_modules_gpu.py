@@ -163,15 +163,22 @@ def test_clip_model_train_mode_several_clips_gpu_vs_cpu_backend():
     assert len(got) == 16
     for a, b in zip(got, want):
         close(a, b, rtol=2e-4, atol=1e-5)      # train-mode BatchNorm over few samples amplifies fp32 rounding: measured <= 6.4e-5
-    # the whole coordinate-only part of the trunk (every level's FPS, ball queries, 3-NN weights) issued ahead on a third
-    # stream: the same numbers, bit for bit (pcdet/models/backbones_3d/pointnet2_backbone.py: PointNet2MSG.geometry)
-    assert gm.geometry_ahead == "fps1"
-    gm.geometry_ahead = "all"
+    # That was the forked schedule with the whole coordinate-only part of the trunk (every level's FPS, ball queries, 3-NN
+    # weights) issued ahead on the geometry stream (pcdet/models/backbones_3d/pointnet2_backbone.py: PointNet2MSG.geometry).
+    # The same schedule with that part computed in line by the SA / FP modules, and the serial schedule: the same numbers, bit
+    # for bit
+    assert gb["points"].shape[0] == 6 <= gm.geometry_stream_max_clouds and gm._geometry_stream is not None
+    gm.geometry_stream_max_clouds = 0
     with torch.no_grad():
-        ahead = gm(gb)
+        inline = gm(gb)
+    gm.overlap_branches = False
+    with torch.no_grad():
+        serial = gm(gb)
     torch.cuda.synchronize()
-    for a, b in zip(ahead, got):
-        assert torch.equal(a, b)
+    assert len(inline) == len(serial) == 16
+    for a, b, c in zip(inline, serial, got):
+        assert torch.equal(a, c)
+        assert torch.equal(b, c)
 
 
 def _reference_style_batch(seed, n_actors, n_points, route, ds):
