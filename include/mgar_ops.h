@@ -31,8 +31,9 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
+#define MGAR_ABI_VERSION 13     /* bumped on any signature change; mgar_abi_version() returns it */
 
-/* Library identity: ABI version (bumped on any signature change) and a static
+/* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
 int mgar_abi_version(void);
 const char *mgar_last_error(void);

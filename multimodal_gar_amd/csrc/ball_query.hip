@@ -295,8 +295,8 @@ static int bq_check(int nsample) {
 
 using namespace mgar;
 
-extern "C" __attribute__((visibility("default"))) int mgar_ball_query_batch(int b, int n, int m, float radius, int nsample, const float *new_xyz,
-                                     const float *xyz, int *idx, void *stream) {
+MGAR_API int mgar_ball_query_batch(int b, int n, int m, float radius, int nsample, const float *new_xyz,
+                                   const float *xyz, int *idx, void *stream) {
     MGAR_REQUIRE(b >= 0 && n >= 0 && m >= 0, "ball_query_batch: negative size");
     if (int e = bq_check(nsample)) return e;
     if (b == 0 || m == 0) return MGAR_OK;
@@ -310,9 +310,9 @@ extern "C" __attribute__((visibility("default"))) int mgar_ball_query_batch(int 
     return check_launch("ball_query_batch: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_ball_query_stack(int B, int M, float radius, int nsample, const float *new_xyz,
-                                     const int *new_xyz_batch_cnt, const float *xyz, const int *xyz_batch_cnt,
-                                     int *idx, void *stream) {
+MGAR_API int mgar_ball_query_stack(int B, int M, float radius, int nsample, const float *new_xyz,
+                                   const int *new_xyz_batch_cnt, const float *xyz, const int *xyz_batch_cnt,
+                                   int *idx, void *stream) {
     MGAR_REQUIRE(B >= 0 && M >= 0, "ball_query_stack: negative size");
     if (int e = bq_check(nsample)) return e;
     if (B == 0 || M == 0) return MGAR_OK;
@@ -329,9 +329,9 @@ extern "C" __attribute__((visibility("default"))) int mgar_ball_query_stack(int 
 
 // Several (radius, nsample) pairs against the same centres and cloud in one scan: idx[r] (b,m,nsample[r])
 // gets exactly what mgar_ball_query_batch(radius[r], nsample[r]) writes.  2 <= nr <= 4.
-extern "C" __attribute__((visibility("default"))) int mgar_ball_query_multi_batch(int b, int n, int m, int nr, const float *radii,
-                                                                                 const int *nsamples, const float *new_xyz,
-                                                                                 const float *xyz, int *const *idx, void *stream) {
+MGAR_API int mgar_ball_query_multi_batch(int b, int n, int m, int nr, const float *radii,
+                                         const int *nsamples, const float *new_xyz,
+                                         const float *xyz, int *const *idx, void *stream) {
     MGAR_REQUIRE(b >= 0 && n >= 0 && m >= 0, "ball_query_multi_batch: negative size");
     MGAR_REQUIRE(nr >= 2 && nr <= BQ_MAX_RADII && radii && nsamples && idx, "ball_query_multi_batch: 2 <= nr <= 4 radii");
     for (int r = 0; r < nr; ++r)
@@ -346,11 +346,11 @@ extern "C" __attribute__((visibility("default"))) int mgar_ball_query_multi_batc
                                   (hipStream_t)stream, "ball_query_multi_batch: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_ball_query_multi_stack(int B, int M, int nr, const float *radii,
-                                                                                 const int *nsamples, const float *new_xyz,
-                                                                                 const int *new_xyz_batch_cnt, const float *xyz,
-                                                                                 const int *xyz_batch_cnt, int *const *idx,
-                                                                                 void *stream) {
+MGAR_API int mgar_ball_query_multi_stack(int B, int M, int nr, const float *radii,
+                                         const int *nsamples, const float *new_xyz,
+                                         const int *new_xyz_batch_cnt, const float *xyz,
+                                         const int *xyz_batch_cnt, int *const *idx,
+                                         void *stream) {
     MGAR_REQUIRE(B >= 0 && M >= 0, "ball_query_multi_stack: negative size");
     MGAR_REQUIRE(nr >= 2 && nr <= BQ_MAX_RADII && radii && nsamples && idx, "ball_query_multi_stack: 2 <= nr <= 4 radii");
     for (int r = 0; r < nr; ++r)

@@ -404,9 +404,7 @@ __global__ __launch_bounds__(BQG_THREADS) void three_nn_grid_kernel(int B, int n
 
 using namespace mgar;
 
-#define BQG_API extern "C" __attribute__((visibility("default")))
-
-BQG_API long long mgar_point_grid_workspace_bytes(int B, long long n_total) {
+MGAR_API long long mgar_point_grid_workspace_bytes(int B, long long n_total) {
     if (B < 0 || n_total < 0) return -1;
     return (long long)pg_layout(B, n_total).total;
 }
@@ -416,8 +414,8 @@ BQG_API long long mgar_point_grid_workspace_bytes(int B, long long n_total) {
 // Batch layout: n_batch > 0 points per cloud, xyz_batch_cnt == NULL; stack layout: n_batch == 0, xyz_batch_cnt (B) on the device.
 // n_total = rows of xyz.  workspace: mgar_point_grid_workspace_bytes(B, n_total) bytes, 16-byte aligned; it is what
 // mgar_ball_query_grid_* take, valid for as long as xyz is unchanged.
-BQG_API int mgar_point_grid_build(int B, int n_batch, long long n_total, const float *xyz, const int *xyz_batch_cnt, float cell,
-                                  void *workspace, void *stream) {
+MGAR_API int mgar_point_grid_build(int B, int n_batch, long long n_total, const float *xyz, const int *xyz_batch_cnt, float cell,
+                                   void *workspace, void *stream) {
     MGAR_REQUIRE(B >= 0 && n_batch >= 0 && n_total >= 0 && cell == cell, "point_grid_build: bad sizes");
     if (B == 0 || n_total == 0) return MGAR_OK;
     MGAR_REQUIRE(xyz && workspace && (n_batch > 0 || xyz_batch_cnt), "point_grid_build: null pointer");
@@ -468,8 +466,8 @@ static int bqg_launch(int B, int m_batch, long long m_total, long long n_total, 
 }
 
 // ball query of mgar_ball_query_batch / _stack through the grid of mgar_point_grid_build (same xyz, same B / n).  nsample <= 64.
-BQG_API int mgar_ball_query_grid_batch(int b, int n, int m, float radius, int nsample, const float *new_xyz, const void *grid, int *idx,
-                                       void *stream) {
+MGAR_API int mgar_ball_query_grid_batch(int b, int n, int m, float radius, int nsample, const float *new_xyz, const void *grid, int *idx,
+                                        void *stream) {
     MGAR_REQUIRE(b >= 0 && n >= 0 && m >= 0 && radius >= 0.f, "ball_query_grid_batch: bad sizes");
     if (nsample < 1 || nsample > 64) { set_error("ball_query_grid: nsample outside [1, 64] (use mgar_ball_query_batch)"); return MGAR_EUNSUPPORTED; }
     if (b == 0 || m == 0) return MGAR_OK;
@@ -477,8 +475,8 @@ BQG_API int mgar_ball_query_grid_batch(int b, int n, int m, float radius, int ns
     if (n == 0) return MGAR_OK;
     return bqg_launch<false>(b, m, (long long)b * m, (long long)b * n, radius, nsample, new_xyz, nullptr, grid, idx, stream);
 }
-BQG_API int mgar_ball_query_grid_stack(int B, int M, long long n_total, float radius, int nsample, const float *new_xyz,
-                                       const int *new_xyz_batch_cnt, const void *grid, int *idx, void *stream) {
+MGAR_API int mgar_ball_query_grid_stack(int B, int M, long long n_total, float radius, int nsample, const float *new_xyz,
+                                        const int *new_xyz_batch_cnt, const void *grid, int *idx, void *stream) {
     MGAR_REQUIRE(B >= 0 && M >= 0 && n_total >= 0 && radius >= 0.f, "ball_query_grid_stack: bad sizes");
     if (nsample < 1 || nsample > 64) { set_error("ball_query_grid: nsample outside [1, 64] (use mgar_ball_query_stack)"); return MGAR_EUNSUPPORTED; }
     if (B == 0 || M == 0) return MGAR_OK;
@@ -493,7 +491,7 @@ BQG_API int mgar_ball_query_grid_stack(int B, int M, long long n_total, float ra
 
 // three_nn of mgar_three_nn_batch / _stack through a grid built over the KNOWN points (mgar_point_grid_build(known ...); cell <= 0
 // lets the library size the cells).  dist2 (.., 3) squared distances, idx (.., 3) (stack: global rows), as the scan kernels.
-BQG_API int mgar_three_nn_grid_batch(int b, int n, int m, const float *unknown, const void *grid, float *dist2, int *idx, void *stream) {
+MGAR_API int mgar_three_nn_grid_batch(int b, int n, int m, const float *unknown, const void *grid, float *dist2, int *idx, void *stream) {
     MGAR_REQUIRE(b >= 0 && n >= 0 && m >= 0, "three_nn_grid_batch: negative size");
     if (b == 0 || n == 0) return MGAR_OK;
     MGAR_REQUIRE(unknown && dist2 && idx && grid && m > 0, "three_nn_grid_batch: null pointer or no known points (use mgar_three_nn_batch)");
@@ -505,8 +503,8 @@ BQG_API int mgar_three_nn_grid_batch(int b, int n, int m, const float *unknown, 
                        (const PgGeom *)(ws + l.geom), (const int *)(ws + l.cell_start), (const float4 *)(ws + l.sorted), dist2, idx);
     return check_launch("three_nn_grid_batch: launch failed");
 }
-BQG_API int mgar_three_nn_grid_stack(int B, int N, long long m_total, const float *unknown, const int *unknown_batch_cnt, const void *grid,
-                                     float *dist2, int *idx, void *stream) {
+MGAR_API int mgar_three_nn_grid_stack(int B, int N, long long m_total, const float *unknown, const int *unknown_batch_cnt, const void *grid,
+                                      float *dist2, int *idx, void *stream) {
     MGAR_REQUIRE(B >= 0 && N >= 0 && m_total >= 0, "three_nn_grid_stack: negative size");
     if (B == 0 || N == 0) return MGAR_OK;
     MGAR_REQUIRE(unknown && unknown_batch_cnt && dist2 && idx && grid && m_total > 0,

@@ -564,9 +564,7 @@ static inline int bn_chunk_bwd(int C, long long n) {
 
 using namespace mgar;
 
-#define BN_API extern "C" __attribute__((visibility("default")))
-
-BN_API int mgar_bn_workspace_floats(int B, int C, int P) {
+MGAR_API int mgar_bn_workspace_floats(int B, int C, int P) {
     if (B < 0 || C < 0 || P < 0) return MGAR_EINVAL;
     int nc = bn_nchunk_fwd(B, C, P) > bn_nchunk(B, P) ? bn_nchunk_fwd(B, C, P) : bn_nchunk(B, P);
     const int small = 4096 / (C > 0 ? C : 1) + 2;   // bound of the chunk count of a reduction over fewer elements (bn_chunk_bwd)
@@ -746,8 +744,8 @@ static int bn_act_maxpool_bwd_impl(const T *dpool, const T *pooled, const unsign
 // ---- C ABI: fp32 payload (include/mgar_ops.h) and the bf16-payload twins (suffix _bf16; same arguments, the payload
 // pointers -- x, y, out, xarg, dy, dx, dpool, pooled -- address bf16 elements) ----
 #define BN_BOTH(NAME, PARAMS_F, PARAMS_B, CALL_F, CALL_B)      \
-    BN_API int NAME PARAMS_F { return CALL_F; }                  \
-    BN_API int NAME##_bf16 PARAMS_B { return CALL_B; }
+    MGAR_API int NAME PARAMS_F { return CALL_F; }                \
+    MGAR_API int NAME##_bf16 PARAMS_B { return CALL_B; }
 typedef const bf16_t *cbf;
 typedef bf16_t *mbf;
 
@@ -852,9 +850,9 @@ BN_BOTH(mgar_bn_act_maxpool_bwd,
         bn_act_maxpool_bwd_impl<bf16_t>((cbf)dpool, (cbf)pooled, arg, (cbf)x, (cbf)xarg, B, C, M, nsample, mean, invstd, gamma, relu, workspace, dgamma, dbeta, (mbf)dx, stream))
 
 // bn_act_bwd with the input gradient written ROW-MAJOR: dx_t (B*P, C) instead of dx (B, C, P).  fp32, C <= 64.
-BN_API int mgar_bn_act_bwd_rowmajor(const float *dy, const float *x, int B, int C, int P, const float *mean, const float *invstd,
-                                    const float *gamma, const float *beta, int relu, float *workspace, float *dgamma, float *dbeta,
-                                    float *dx_t, void *stream) {
+MGAR_API int mgar_bn_act_bwd_rowmajor(const float *dy, const float *x, int B, int C, int P, const float *mean, const float *invstd,
+                                      const float *gamma, const float *beta, int relu, float *workspace, float *dgamma, float *dbeta,
+                                      float *dx_t, void *stream) {
     MGAR_REQUIRE(bn_sizes_ok(B, C, P), "bn_act_bwd_rowmajor: bad sizes");
     if (C > 64) {
         set_error("bn_act_bwd_rowmajor: C <= 64");
@@ -883,10 +881,10 @@ BN_API int mgar_bn_act_bwd_rowmajor(const float *dy, const float *x, int B, int 
 // Covers the two layouts the pooled gradient arrives in: a channel slice of a wider (B, C_total, M) tensor (the gradient
 // of the torch.cat over the scales of an SA module) and the transposed view of (M, C_total) rows (the RoI-grid lift's
 // consumer works on rows).  fp32.
-BN_API int mgar_bn_act_maxpool_bwd_strided(const float *dpool, long long sb, long long sc, long long sm, const float *pooled,
-                                           const unsigned char *arg, const float *x, const float *xarg, int B, int C, int M,
-                                           int nsample, const float *mean, const float *invstd, const float *gamma, int relu,
-                                           float *workspace, float *dgamma, float *dbeta, float *dx, void *stream) {
+MGAR_API int mgar_bn_act_maxpool_bwd_strided(const float *dpool, long long sb, long long sc, long long sm, const float *pooled,
+                                             const unsigned char *arg, const float *x, const float *xarg, int B, int C, int M,
+                                             int nsample, const float *mean, const float *invstd, const float *gamma, int relu,
+                                             float *workspace, float *dgamma, float *dbeta, float *dx, void *stream) {
     MGAR_REQUIRE(sb >= 0 && sc >= 1 && sm >= 1, "bn_act_maxpool_bwd_strided: bad strides");
     return bn_act_maxpool_bwd_impl<float>(dpool, pooled, arg, x, xarg, B, C, M, nsample, mean, invstd, gamma, relu, workspace, dgamma,
                                           dbeta, dx, stream, sb, sc, sm);
@@ -929,13 +927,13 @@ __global__ __launch_bounds__(64) void bn_merge_partials_kernel(const float *__re
 // channel in (b, p) order) the chunk's mean and sum of squared deviations; n = B * P elements per channel = nchunk * chunk.
 // Same finalize (Chan merge in double, running statistics) as mgar_bn_train_stats, without its pass over x.
 // workspace: mgar_bn_stats_from_partials_workspace_floats(nchunk, C) floats (many partials are first merged in groups).
-BN_API long long mgar_bn_stats_from_partials_workspace_floats(int nchunk, int C) {
+MGAR_API long long mgar_bn_stats_from_partials_workspace_floats(int nchunk, int C) {
     if (nchunk < 0 || C < 0) return -1;
     return nchunk > 4 * BN_MERGE_G ? 2ll * C * ((nchunk + BN_MERGE_G - 1) / BN_MERGE_G) : 0;
 }
-BN_API int mgar_bn_stats_from_partials(const float *partial, int nchunk, int C, long long n, int chunk, float eps, float momentum,
-                                       float *workspace, float *mean, float *invstd, float *running_mean, float *running_var,
-                                       long long *num_batches_tracked, void *stream) {
+MGAR_API int mgar_bn_stats_from_partials(const float *partial, int nchunk, int C, long long n, int chunk, float eps, float momentum,
+                                         float *workspace, float *mean, float *invstd, float *running_mean, float *running_var,
+                                         long long *num_batches_tracked, void *stream) {
     MGAR_REQUIRE(nchunk >= 0 && C >= 0 && n >= 0 && chunk >= 1, "bn_stats_from_partials: bad sizes");
     if (C == 0 || n == 0) return MGAR_OK;
     MGAR_REQUIRE(partial && mean && invstd, "bn_stats_from_partials: null pointer");
@@ -958,9 +956,9 @@ BN_API int mgar_bn_stats_from_partials(const float *partial, int nchunk, int C, 
 
 // BatchNorm [+ ReLU] backward, APPLY ONLY: the reduction {mean dz, mean dz xhat} per channel comes in `coef` (2 C floats) from
 // the kernel that already had the operands in hand (mgar_pointwise_conv_dw_bnbwd).  rowmajor != 0: dx_t (B * P, C), C <= 64.
-BN_API int mgar_bn_act_bwd_apply(const float *dy, const float *x, int B, int C, int P, const float *mean, const float *invstd,
-                                 const float *gamma, const float *beta, int relu, const float *coef, int rowmajor, float *dx,
-                                 void *stream) {
+MGAR_API int mgar_bn_act_bwd_apply(const float *dy, const float *x, int B, int C, int P, const float *mean, const float *invstd,
+                                   const float *gamma, const float *beta, int relu, const float *coef, int rowmajor, float *dx,
+                                   void *stream) {
     MGAR_REQUIRE(bn_sizes_ok(B, C, P), "bn_act_bwd_apply: bad sizes");
     if ((long long)B * C * P == 0) return MGAR_OK;
     MGAR_REQUIRE(dy && x && mean && invstd && coef && dx, "bn_act_bwd_apply: null pointer");

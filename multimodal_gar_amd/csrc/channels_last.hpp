@@ -239,12 +239,10 @@ __global__ __launch_bounds__(CL_THREADS) void bn_rows_bwd_apply_kernel(const flo
 
 }  // namespace mgar
 
-#define CL_API extern "C" __attribute__((visibility("default")))
-
 static bool cl_shape_ok(int S, int R, int C) { return S >= 0 && R >= 0 && C >= 0 && C % 4 == 0 && C <= 1024; }
 
 // floats of workspace for mgar_bn_cl_train_stats (partials + the per-sample variances)
-CL_API long long mgar_bn_cl_workspace_floats(int S, int R, int C, int per_sample) {
+MGAR_API long long mgar_bn_cl_workspace_floats(int S, int R, int C, int per_sample) {
     if (!cl_shape_ok(S, R, C) || S == 0 || R == 0) return 0;
     const int Ss = per_sample ? S : 1;
     const long long Rs = per_sample ? R : (long long)S * R;
@@ -334,52 +332,52 @@ static int maxpool3d_cl_impl(const T *x, int N, int T_, int H, int W, int C, int
 }
 
 // ---- C ABI (include/mgar_ops.h); _bf16 twins: x / y address bf16 elements, statistics stay fp32 --------------------------------
-CL_API int mgar_bn_cl_train_stats(const float *x, int S, int R, int C, int per_sample, float eps, float momentum, float *workspace,
-                                  float *mean, float *invstd, float *running_mean, float *running_var,
-                                  long long *num_batches_tracked, void *stream) {
+MGAR_API int mgar_bn_cl_train_stats(const float *x, int S, int R, int C, int per_sample, float eps, float momentum, float *workspace,
+                                    float *mean, float *invstd, float *running_mean, float *running_var,
+                                    long long *num_batches_tracked, void *stream) {
     return bn_cl_train_stats_impl<float>(x, S, R, C, per_sample, eps, momentum, workspace, mean, invstd, running_mean, running_var,
                                          num_batches_tracked, stream);
 }
-CL_API int mgar_bn_cl_train_stats_bf16(const void *x, int S, int R, int C, int per_sample, float eps, float momentum, float *workspace,
-                                       float *mean, float *invstd, float *running_mean, float *running_var,
-                                       long long *num_batches_tracked, void *stream) {
+MGAR_API int mgar_bn_cl_train_stats_bf16(const void *x, int S, int R, int C, int per_sample, float eps, float momentum, float *workspace,
+                                         float *mean, float *invstd, float *running_mean, float *running_var,
+                                         long long *num_batches_tracked, void *stream) {
     return bn_cl_train_stats_impl<bf16_t>((const bf16_t *)x, S, R, C, per_sample, eps, momentum, workspace, mean, invstd, running_mean,
                                           running_var, num_batches_tracked, stream);
 }
-CL_API int mgar_bn_cl_act_fwd(const float *x, int S, int R, int C, int per_sample, const float *mean, const float *invstd,
-                              const float *gamma, const float *beta, int relu, float *y, int ldy, void *stream) {
+MGAR_API int mgar_bn_cl_act_fwd(const float *x, int S, int R, int C, int per_sample, const float *mean, const float *invstd,
+                                const float *gamma, const float *beta, int relu, float *y, int ldy, void *stream) {
     return bn_cl_act_fwd_impl<float>(x, S, R, C, per_sample, mean, invstd, gamma, beta, relu, y, ldy, stream);
 }
-CL_API int mgar_bn_cl_act_fwd_bf16(const void *x, int S, int R, int C, int per_sample, const float *mean, const float *invstd,
-                                   const float *gamma, const float *beta, int relu, void *y, int ldy, void *stream) {
+MGAR_API int mgar_bn_cl_act_fwd_bf16(const void *x, int S, int R, int C, int per_sample, const float *mean, const float *invstd,
+                                     const float *gamma, const float *beta, int relu, void *y, int ldy, void *stream) {
     return bn_cl_act_fwd_impl<bf16_t>((const bf16_t *)x, S, R, C, per_sample, mean, invstd, gamma, beta, relu, (bf16_t *)y, ldy, stream);
 }
-CL_API int mgar_bn_act_fwd_to_cl(const float *x, int S, int C, int R, int per_sample, const float *mean, const float *invstd,
-                                 const float *gamma, const float *beta, int relu, float *y, int ldy, void *stream) {
+MGAR_API int mgar_bn_act_fwd_to_cl(const float *x, int S, int C, int R, int per_sample, const float *mean, const float *invstd,
+                                   const float *gamma, const float *beta, int relu, float *y, int ldy, void *stream) {
     return bn_act_fwd_to_cl_impl<float>(x, S, C, R, per_sample, mean, invstd, gamma, beta, relu, y, ldy, stream);
 }
-CL_API int mgar_bn_act_fwd_to_cl_bf16(const void *x, int S, int C, int R, int per_sample, const float *mean, const float *invstd,
-                                      const float *gamma, const float *beta, int relu, void *y, int ldy, void *stream) {
+MGAR_API int mgar_bn_act_fwd_to_cl_bf16(const void *x, int S, int C, int R, int per_sample, const float *mean, const float *invstd,
+                                        const float *gamma, const float *beta, int relu, void *y, int ldy, void *stream) {
     return bn_act_fwd_to_cl_impl<bf16_t>((const bf16_t *)x, S, C, R, per_sample, mean, invstd, gamma, beta, relu, (bf16_t *)y, ldy, stream);
 }
-CL_API int mgar_maxpool3d_same_fwd_cl(const float *x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw,
-                                      float *y, void *stream) {
+MGAR_API int mgar_maxpool3d_same_fwd_cl(const float *x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw,
+                                        float *y, void *stream) {
     return maxpool3d_cl_impl<float>(x, N, T, H, W, C, kt, kh, kw, st, sh, sw, y, stream);
 }
-CL_API int mgar_maxpool3d_same_fwd_cl_bf16(const void *x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh,
-                                           int sw, void *y, void *stream) {
+MGAR_API int mgar_maxpool3d_same_fwd_cl_bf16(const void *x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh,
+                                             int sw, void *y, void *stream) {
     return maxpool3d_cl_impl<bf16_t>((const bf16_t *)x, N, T, H, W, C, kt, kh, kw, st, sh, sw, (bf16_t *)y, stream);
 }
 
 // BatchNorm1d(train) [+ ReLU] backward over ROW-MAJOR x, dy (rows, C) fp32 (the sparse trunk's features): dx (rows, C), dgamma,
 // dbeta (C).  workspace: mgar_bn_rows_bwd_workspace_floats(rows, C) floats.  C % 4 == 0, C <= 1024.
-CL_API long long mgar_bn_rows_bwd_workspace_floats(int rows, int C) {
+MGAR_API long long mgar_bn_rows_bwd_workspace_floats(int rows, int C) {
     if (!cl_shape_ok(1, rows, C)) return -1;
     const int chunk = cl_chunk_rows(1, rows), nchunk = (rows + chunk - 1) / chunk;
     return 2ll * C * (nchunk > 0 ? nchunk : 1) + 2ll * C;
 }
-CL_API int mgar_bn_rows_bwd(const float *dy, const float *x, int rows, int C, const float *mean, const float *invstd, const float *gamma,
-                            const float *beta, int relu, float *workspace, float *dgamma, float *dbeta, float *dx, void *stream) {
+MGAR_API int mgar_bn_rows_bwd(const float *dy, const float *x, int rows, int C, const float *mean, const float *invstd, const float *gamma,
+                              const float *beta, int relu, float *workspace, float *dgamma, float *dbeta, float *dx, void *stream) {
     MGAR_REQUIRE(cl_shape_ok(1, rows, C), "bn_rows_bwd: needs C % 4 == 0, C <= 1024");
     if ((long long)rows * C == 0) return MGAR_OK;
     MGAR_REQUIRE(dy && x && mean && invstd && workspace && dx, "bn_rows_bwd: null pointer");

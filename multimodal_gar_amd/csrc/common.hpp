@@ -5,6 +5,9 @@
 #include <stdint.h>
 #include "../../include/mgar_ops.h"
 
+// every definition of an entry point of mgar_ops.h (the library is compiled with -fvisibility=hidden)
+#define MGAR_API extern "C" __attribute__((visibility("default")))
+
 namespace mgar {
 
 constexpr int kWave = 64;

@@ -252,15 +252,13 @@ static void cw_launch(const float *x, const float *wt, CwArgs a, float *y, hipSt
 
 using namespace mgar;
 
-#define CW_API extern "C" __attribute__((visibility("default")))
-
 // floats of the transformed-filter scratch mgar_conv3d_k3_fwd needs (rewritten on every call)
-CW_API long long mgar_conv3d_k3_workspace_floats(int Cin, int Cout) {
+MGAR_API long long mgar_conv3d_k3_workspace_floats(int Cin, int Cout) {
     if (Cin <= 0 || Cout <= 0) return 0;
     return (long long)ceil_div(Cout, CW_CG) * CW_CG * Cin * 36;
 }
 
-CW_API int mgar_conv3d_k3_set_lds_pad(int bytes) {
+MGAR_API int mgar_conv3d_k3_set_lds_pad(int bytes) {
     MGAR_REQUIRE(bytes >= 0 && bytes <= 90 * 1024, "conv3d_k3_set_lds_pad: 0 .. 92160 bytes");
     g_cw_lds_pad = bytes;
     return MGAR_OK;
@@ -268,8 +266,8 @@ CW_API int mgar_conv3d_k3_set_lds_pad(int bytes) {
 
 // x (N, Cin, D, H, W) fp32 NCDHW, w (Cout, Cin, 3, 3, 3) -> y (N, Cout, D, H, W): stride 1, zero padding 1 on every side.
 // Cin and W must be even (every I3D instance is); anything else is MGAR_EINVAL and the caller keeps the library convolution.
-CW_API int mgar_conv3d_k3_fwd(const float *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, float *w_packed, float *y,
-                              void *stream) {
+MGAR_API int mgar_conv3d_k3_fwd(const float *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, float *w_packed, float *y,
+                                void *stream) {
     MGAR_REQUIRE(N >= 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "conv3d_k3_fwd: bad sizes");
     MGAR_REQUIRE(Cin % 2 == 0 && W % 2 == 0, "conv3d_k3_fwd: Cin and W must be even");
     if (N == 0) return MGAR_OK;

@@ -209,10 +209,10 @@ __global__ __launch_bounds__(256) void dafm_bwd_cols_kernel(int S, int total_row
 
 using namespace mgar;
 
-extern "C" __attribute__((visibility("default"))) int mgar_dafm_attn_fwd(int S, int total_rows, int D, const int *scene_off,
-                                                                        const int *de_off, const float *q, const float *k,
-                                                                        const float *v, const float *de, float sigma,
-                                                                        float scale, float *att, float *out, void *stream) {
+MGAR_API int mgar_dafm_attn_fwd(int S, int total_rows, int D, const int *scene_off,
+                                const int *de_off, const float *q, const float *k,
+                                const float *v, const float *de, float sigma,
+                                float scale, float *att, float *out, void *stream) {
     MGAR_REQUIRE(S >= 0 && total_rows >= 0 && D > 0 && D % 64 == 0, "dafm_attn_fwd: bad sizes (D must be a multiple of 64)");
     MGAR_REQUIRE(sigma != 0.f, "dafm_attn_fwd: sigma == 0");
     if (S == 0 || total_rows == 0) return MGAR_OK;
@@ -226,12 +226,12 @@ extern "C" __attribute__((visibility("default"))) int mgar_dafm_attn_fwd(int S, 
     return check_launch("dafm_attn_fwd: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_dafm_attn_bwd(int S, int total_rows, int D, const int *scene_off,
-                                                                        const int *de_off, const float *q, const float *k,
-                                                                        const float *v, const float *de, float sigma,
-                                                                        float scale, const float *att, const float *grad_out,
-                                                                        float *gmat, float *grad_q, float *grad_k,
-                                                                        float *grad_v, void *stream) {
+MGAR_API int mgar_dafm_attn_bwd(int S, int total_rows, int D, const int *scene_off,
+                                const int *de_off, const float *q, const float *k,
+                                const float *v, const float *de, float sigma,
+                                float scale, const float *att, const float *grad_out,
+                                float *gmat, float *grad_q, float *grad_k,
+                                float *grad_v, void *stream) {
     MGAR_REQUIRE(S >= 0 && total_rows >= 0 && D > 0 && D % 64 == 0, "dafm_attn_bwd: bad sizes (D must be a multiple of 64)");
     MGAR_REQUIRE(sigma != 0.f, "dafm_attn_bwd: sigma == 0");
     if (S == 0 || total_rows == 0) return MGAR_OK;

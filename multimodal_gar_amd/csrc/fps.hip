@@ -824,7 +824,7 @@ static int fps_dispatch(int nclouds, int n_max, int bs_log2, const FpsArgs &A, h
 
 using namespace mgar;
 
-extern "C" __attribute__((visibility("default"))) int mgar_fps_batch(int b, int n, int m, const float *points, float *temp, int *idx, void *stream) {
+MGAR_API int mgar_fps_batch(int b, int n, int m, const float *points, float *temp, int *idx, void *stream) {
     MGAR_REQUIRE(b >= 0 && n >= 0 && m >= 0, "fps_batch: negative size");
     if (b == 0 || m == 0) return MGAR_OK;
     MGAR_REQUIRE(n > 0, "fps_batch: m > 0 samples requested from an empty cloud");
@@ -839,8 +839,8 @@ extern "C" __attribute__((visibility("default"))) int mgar_fps_batch(int b, int 
     return fps_dispatch(b, n, bs_log2, A, (hipStream_t)stream);
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_fps_stack(int batch_size, int N, const float *points, float *temp, const int *xyz_batch_cnt,
-                              int *idx, const int *num_sampled_points, void *stream) {
+MGAR_API int mgar_fps_stack(int batch_size, int N, const float *points, float *temp, const int *xyz_batch_cnt,
+                            int *idx, const int *num_sampled_points, void *stream) {
     MGAR_REQUIRE(batch_size >= 0 && N >= 0, "fps_stack: negative size");
     if (batch_size == 0 || N == 0) return MGAR_OK;
     MGAR_REQUIRE(points && temp && idx && xyz_batch_cnt && num_sampled_points, "fps_stack: null pointer");
@@ -850,7 +850,7 @@ extern "C" __attribute__((visibility("default"))) int mgar_fps_stack(int batch_s
 }
 
 // Morton codes of every point (sort them per cloud to obtain the `perm` of mgar_fps_batch_perm).
-extern "C" __attribute__((visibility("default"))) int mgar_morton_codes(int b, int n, const float *points, int *codes, void *stream) {
+MGAR_API int mgar_morton_codes(int b, int n, const float *points, int *codes, void *stream) {
     MGAR_REQUIRE(b >= 0 && n >= 0, "morton_codes: negative size");
     if ((long long)b * n == 0) return MGAR_OK;
     MGAR_REQUIRE(points && codes, "morton_codes: null pointer");
@@ -860,8 +860,8 @@ extern "C" __attribute__((visibility("default"))) int mgar_morton_codes(int b, i
 
 // mgar_fps_batch with spatial pruning: perm (b, n) lists each cloud's point indices in a spatially
 // coherent order (any permutation gives the same, exact result; a Morton order makes it fast).
-extern "C" __attribute__((visibility("default"))) int mgar_fps_batch_perm(int b, int n, int m, const float *points, float *temp, const int *perm,
-                                                                         int *idx, void *stream) {
+MGAR_API int mgar_fps_batch_perm(int b, int n, int m, const float *points, float *temp, const int *perm,
+                                 int *idx, void *stream) {
     MGAR_REQUIRE(b >= 0 && n >= 0 && m >= 0, "fps_batch_perm: negative size");
     if (b == 0 || m == 0) return MGAR_OK;
     MGAR_REQUIRE(n > 0, "fps_batch_perm: m > 0 samples requested from an empty cloud");
@@ -883,13 +883,13 @@ extern "C" __attribute__((visibility("default"))) int mgar_fps_batch_perm(int b,
 
 // Clouds of 16 385 .. 65 536 points, any permutation `perm` (a Morton order is fast): see fps_bucket_kernel.
 // workspace: mgar_fps_batch_buckets_workspace_floats(b, n) floats, 16-byte aligned.
-extern "C" __attribute__((visibility("default"))) long long mgar_fps_batch_buckets_workspace_floats(int b, int n) {
+MGAR_API long long mgar_fps_batch_buckets_workspace_floats(int b, int n) {
     if (b < 0 || n < 0) return -1;
     const int cap = n <= 32768 ? 32768 : 65536;
     return (long long)b * cap * 4;
 }
-extern "C" __attribute__((visibility("default"))) int mgar_fps_batch_buckets(int b, int n, int m, const float *points, float *temp,
-                                                                            const int *perm, float *workspace, int *idx, void *stream) {
+MGAR_API int mgar_fps_batch_buckets(int b, int n, int m, const float *points, float *temp,
+                                    const int *perm, float *workspace, int *idx, void *stream) {
     MGAR_REQUIRE(b >= 0 && n >= 0 && m >= 0, "fps_batch_buckets: negative size");
     if (b == 0 || m == 0) return MGAR_OK;
     MGAR_REQUIRE(points && temp && idx && perm && workspace, "fps_batch_buckets: null pointer");

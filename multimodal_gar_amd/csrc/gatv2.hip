@@ -206,11 +206,11 @@ using namespace mgar;
         default: set_error("gatv2: C must be 64, 128, 256, 512 or 1024"); return MGAR_EUNSUPPORTED;       \
     }
 
-extern "C" __attribute__((visibility("default"))) int mgar_gatv2_fwd(int n_nodes, int H, int C, const int *rowptr,
-                                                                    const int *col, const float *xl, const float *xr,
-                                                                    const float *att, float slope,
-                                                                    const float *edge_scale, float *alpha, float *out,
-                                                                    void *stream) {
+MGAR_API int mgar_gatv2_fwd(int n_nodes, int H, int C, const int *rowptr,
+                            const int *col, const float *xl, const float *xr,
+                            const float *att, float slope,
+                            const float *edge_scale, float *alpha, float *out,
+                            void *stream) {
     MGAR_REQUIRE(n_nodes >= 0 && H > 0 && C > 0, "gatv2_fwd: bad sizes");
     if (n_nodes == 0) return MGAR_OK;
     MGAR_REQUIRE(rowptr && col && xl && xr && att && alpha && out, "gatv2_fwd: null pointer");
@@ -224,13 +224,13 @@ extern "C" __attribute__((visibility("default"))) int mgar_gatv2_fwd(int n_nodes
     return check_launch("gatv2_fwd: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_gatv2_bwd(int n_nodes, int H, int C, const int *rowptr,
-                                                                    const int *col, const int *src_rowptr,
-                                                                    const int *src_edge, const int *src_dst, const float *xl,
-                                                                    const float *xr, const float *att, float slope,
-                                                                    const float *edge_scale, const float *alpha,
-                                                                    const float *grad_out, float *workspace, float *grad_xl,
-                                                                    float *grad_xr, float *grad_att, void *stream) {
+MGAR_API int mgar_gatv2_bwd(int n_nodes, int H, int C, const int *rowptr,
+                            const int *col, const int *src_rowptr,
+                            const int *src_edge, const int *src_dst, const float *xl,
+                            const float *xr, const float *att, float slope,
+                            const float *edge_scale, const float *alpha,
+                            const float *grad_out, float *workspace, float *grad_xl,
+                            float *grad_xr, float *grad_att, void *stream) {
     MGAR_REQUIRE(n_nodes >= 0 && H > 0 && C > 0, "gatv2_bwd: bad sizes");
     if (n_nodes == 0) return MGAR_OK;
     MGAR_REQUIRE(rowptr && col && src_rowptr && src_edge && src_dst && xl && xr && att && alpha && grad_out && workspace && grad_xl &&
@@ -254,7 +254,7 @@ extern "C" __attribute__((visibility("default"))) int mgar_gatv2_bwd(int n_nodes
     return check_launch("gatv2_bwd: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) long long mgar_gatv2_bwd_workspace_floats(int n_nodes, int H, int C, int n_edges) {
+MGAR_API long long mgar_gatv2_bwd_workspace_floats(int n_nodes, int H, int C, int n_edges) {
     if (n_nodes < 0 || H <= 0 || C <= 0 || n_edges < 0) return -1;
     return (long long)n_nodes * H * C + (long long)n_edges * H;
 }

@@ -191,8 +191,8 @@ static int launch_group_batch_bwd(int b, int c, int n, int cols, const float *gr
 
 using namespace mgar;
 
-extern "C" __attribute__((visibility("default"))) int mgar_group_points_batch(int b, int c, int n, int npoints, int nsample, const float *points,
-                                       const int *idx, float *out, void *stream) {
+MGAR_API int mgar_group_points_batch(int b, int c, int n, int npoints, int nsample, const float *points,
+                                     const int *idx, float *out, void *stream) {
     MGAR_REQUIRE(b >= 0 && c >= 0 && n >= 0 && npoints >= 0 && nsample >= 0, "group_points_batch: negative size");
     MGAR_REQUIRE(b <= 65535, "group_points_batch: b > 65535");
     if ((long long)b * c * npoints * nsample == 0) return MGAR_OK;
@@ -200,8 +200,8 @@ extern "C" __attribute__((visibility("default"))) int mgar_group_points_batch(in
     return launch_group_batch_fwd(b, c, n, npoints * nsample, points, idx, out, (hipStream_t)stream);
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_group_points_grad_batch(int b, int c, int n, int npoints, int nsample, const float *grad_out,
-                                            const int *idx, float *grad_points, void *stream) {
+MGAR_API int mgar_group_points_grad_batch(int b, int c, int n, int npoints, int nsample, const float *grad_out,
+                                          const int *idx, float *grad_points, void *stream) {
     MGAR_REQUIRE(b >= 0 && c >= 0 && n >= 0 && npoints >= 0 && nsample >= 0, "group_points_grad_batch: negative size");
     MGAR_REQUIRE(b <= 65535 && c <= 65535, "group_points_grad_batch: b or c > 65535");
     if ((long long)b * c * npoints * nsample == 0) return MGAR_OK;
@@ -209,8 +209,8 @@ extern "C" __attribute__((visibility("default"))) int mgar_group_points_grad_bat
     return launch_group_batch_bwd(b, c, n, npoints * nsample, grad_out, idx, grad_points, (hipStream_t)stream);
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_gather_points_batch(int b, int c, int n, int npoints, const float *points, const int *idx,
-                                        float *out, void *stream) {
+MGAR_API int mgar_gather_points_batch(int b, int c, int n, int npoints, const float *points, const int *idx,
+                                      float *out, void *stream) {
     MGAR_REQUIRE(b >= 0 && c >= 0 && n >= 0 && npoints >= 0, "gather_points_batch: negative size");
     MGAR_REQUIRE(b <= 65535, "gather_points_batch: b > 65535");
     if ((long long)b * c * npoints == 0) return MGAR_OK;
@@ -218,8 +218,8 @@ extern "C" __attribute__((visibility("default"))) int mgar_gather_points_batch(i
     return launch_group_batch_fwd(b, c, n, npoints, points, idx, out, (hipStream_t)stream);
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_gather_points_grad_batch(int b, int c, int n, int npoints, const float *grad_out, const int *idx,
-                                             float *grad_points, void *stream) {
+MGAR_API int mgar_gather_points_grad_batch(int b, int c, int n, int npoints, const float *grad_out, const int *idx,
+                                           float *grad_points, void *stream) {
     MGAR_REQUIRE(b >= 0 && c >= 0 && n >= 0 && npoints >= 0, "gather_points_grad_batch: negative size");
     MGAR_REQUIRE(b <= 65535 && c <= 65535, "gather_points_grad_batch: b or c > 65535");
     if ((long long)b * c * npoints == 0) return MGAR_OK;
@@ -227,9 +227,9 @@ extern "C" __attribute__((visibility("default"))) int mgar_gather_points_grad_ba
     return launch_group_batch_bwd(b, c, n, npoints, grad_out, idx, grad_points, (hipStream_t)stream);
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_group_points_stack(int B, int M, int C, int nsample, const float *features,
-                                       const int *features_batch_cnt, const int *idx, const int *idx_batch_cnt,
-                                       float *out, void *stream) {
+MGAR_API int mgar_group_points_stack(int B, int M, int C, int nsample, const float *features,
+                                     const int *features_batch_cnt, const int *idx, const int *idx_batch_cnt,
+                                     float *out, void *stream) {
     MGAR_REQUIRE(B >= 0 && M >= 0 && C >= 0 && nsample >= 0, "group_points_stack: negative size");
     if ((long long)M * C * nsample == 0 || B == 0) return MGAR_OK;
     MGAR_REQUIRE(features && features_batch_cnt && idx && idx_batch_cnt && out, "group_points_stack: null pointer");
@@ -244,9 +244,9 @@ extern "C" __attribute__((visibility("default"))) int mgar_group_points_stack(in
     return check_launch("group_points_stack: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_group_points_grad_stack(int B, int M, int C, int N, int nsample, const float *grad_out,
-                                            const int *idx, const int *idx_batch_cnt, const int *features_batch_cnt,
-                                            float *grad_features, void *stream) {
+MGAR_API int mgar_group_points_grad_stack(int B, int M, int C, int N, int nsample, const float *grad_out,
+                                          const int *idx, const int *idx_batch_cnt, const int *features_batch_cnt,
+                                          float *grad_features, void *stream) {
     MGAR_REQUIRE(B >= 0 && M >= 0 && C >= 0 && N >= 0 && nsample >= 0, "group_points_grad_stack: negative size");
     if ((long long)M * C * nsample == 0 || B == 0) return MGAR_OK;
     MGAR_REQUIRE(grad_out && features_batch_cnt && idx && idx_batch_cnt && grad_features,

@@ -367,10 +367,6 @@ __global__ __launch_bounds__(VM_THREADS) void velodyne_write_kernel(MergeArgs a,
 
 using namespace mgar;
 
-#define MGAR_API __attribute__((visibility("default")))
-
-extern "C" {
-
 MGAR_API int mgar_image_resample_ksize(int in_size, int out_size) {
     if (in_size <= 0 || out_size <= 0) return MGAR_EINVAL;
     return resample_ksize(in_size, out_size);
@@ -476,5 +472,3 @@ MGAR_API int mgar_velodyne_merge_crop(int n_upper, int n_lower, int C, const flo
     velodyne_write_kernel<<<nblocks, VM_THREADS, 0, st>>>(a, workspace, out);
     return check_launch("mgar_velodyne_merge_crop: launch failed");
 }
-
-}  // extern "C"

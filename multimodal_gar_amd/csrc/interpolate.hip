@@ -398,8 +398,8 @@ __global__ __launch_bounds__(256) void three_interp_stack_bwd_kernel(long long t
 
 using namespace mgar;
 
-extern "C" __attribute__((visibility("default"))) int mgar_three_nn_batch(int b, int n, int m, const float *unknown, const float *known, float *dist2,
-                                   int *idx, void *stream) {
+MGAR_API int mgar_three_nn_batch(int b, int n, int m, const float *unknown, const float *known, float *dist2,
+                                 int *idx, void *stream) {
     MGAR_REQUIRE(b >= 0 && n >= 0 && m >= 0, "three_nn_batch: negative size");
     MGAR_REQUIRE(b <= 65535, "three_nn_batch: b > 65535");
     if (b == 0 || n == 0) return MGAR_OK;
@@ -411,9 +411,9 @@ extern "C" __attribute__((visibility("default"))) int mgar_three_nn_batch(int b,
     return check_launch("three_nn_batch: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_three_nn_stack(int batch_size, int N, int M, const float *unknown, const int *unknown_batch_cnt,
-                                   const float *known, const int *known_batch_cnt, float *dist2, int *idx,
-                                   void *stream) {
+MGAR_API int mgar_three_nn_stack(int batch_size, int N, int M, const float *unknown, const int *unknown_batch_cnt,
+                                 const float *known, const int *known_batch_cnt, float *dist2, int *idx,
+                                 void *stream) {
     MGAR_REQUIRE(batch_size >= 0 && N >= 0 && M >= 0, "three_nn_stack: negative size");
     if (batch_size == 0 || N == 0) return MGAR_OK;
     MGAR_REQUIRE(unknown && dist2 && idx && unknown_batch_cnt && known_batch_cnt && (known || M == 0),
@@ -457,13 +457,13 @@ static int three_interpolate_batch_impl(int b, int c, int m, int n, const T *poi
     return check_launch("three_interpolate_batch: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_batch(int b, int c, int m, int n, const float *points, const int *idx,
-                                            const float *weight, float *out, void *stream) {
+MGAR_API int mgar_three_interpolate_batch(int b, int c, int m, int n, const float *points, const int *idx,
+                                          const float *weight, float *out, void *stream) {
     return three_interpolate_batch_impl<float>(b, c, m, n, points, idx, weight, out, stream);
 }
 // bf16 payload: points / out address bf16 elements; idx int32, weight fp32
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_batch_bf16(int b, int c, int m, int n, const void *points, const int *idx,
-                                            const float *weight, void *out, void *stream) {
+MGAR_API int mgar_three_interpolate_batch_bf16(int b, int c, int m, int n, const void *points, const int *idx,
+                                               const float *weight, void *out, void *stream) {
     return three_interpolate_batch_impl<bf16_t>(b, c, m, n, (const bf16_t *)points, idx, weight, (bf16_t *)out, stream);
 }
 
@@ -472,31 +472,31 @@ extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_bat
 //     W [interp(f) ; skip] = interp(W_a f) + W_b skip
 // -- the known features are projected on the COARSE level (m columns instead of n), the skip term is one GEMM with K = C_skip, and
 // this kernel adds the interpolation of the projected features into it (reference pointnet2_batch/pointnet2_modules.py:139-150).
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_batch_add(int b, int c, int m, int n, const float *points, const int *idx,
-                                            const float *weight, float *out, void *stream) {
+MGAR_API int mgar_three_interpolate_batch_add(int b, int c, int m, int n, const float *points, const int *idx,
+                                              const float *weight, float *out, void *stream) {
     return three_interpolate_batch_impl<float>(b, c, m, n, points, idx, weight, out, stream, -1, 1);
 }
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_batch_add_bf16(int b, int c, int m, int n, const void *points, const int *idx,
-                                            const float *weight, void *out, void *stream) {
+MGAR_API int mgar_three_interpolate_batch_add_bf16(int b, int c, int m, int n, const void *points, const int *idx,
+                                                   const float *weight, void *out, void *stream) {
     return three_interpolate_batch_impl<bf16_t>(b, c, m, n, (const bf16_t *)points, idx, weight, (bf16_t *)out, stream, -1, 1);
 }
 
 // out a CHANNEL SLICE of a wider (b, c_total, n) tensor (samples out_bstride >= c * n elements apart): the decoder's
 // torch.cat([interpolated, skip]) without the pass that copies the interpolated half
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_batch_into(int b, int c, int m, int n, const float *points, const int *idx,
-                                            const float *weight, float *out, long long out_bstride, void *stream) {
+MGAR_API int mgar_three_interpolate_batch_into(int b, int c, int m, int n, const float *points, const int *idx,
+                                               const float *weight, float *out, long long out_bstride, void *stream) {
     return three_interpolate_batch_impl<float>(b, c, m, n, points, idx, weight, out, stream, out_bstride);
 }
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_batch_into_bf16(int b, int c, int m, int n, const void *points, const int *idx,
-                                            const float *weight, void *out, long long out_bstride, void *stream) {
+MGAR_API int mgar_three_interpolate_batch_into_bf16(int b, int c, int m, int n, const void *points, const int *idx,
+                                                    const float *weight, void *out, long long out_bstride, void *stream) {
     return three_interpolate_batch_impl<bf16_t>(b, c, m, n, (const bf16_t *)points, idx, weight, (bf16_t *)out, stream, out_bstride);
 }
 
 // grad_out_bstride: elements between consecutive samples of grad_out (>= c * n): grad_out may be a channel slice of a wider
 // (b, c_total, n) tensor -- the gradient of the decoder's torch.cat([interpolated, skip]) -- read in place, no copy
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_grad_batch_strided(int b, int c, int n, int m, const float *grad_out,
-                                                 long long grad_out_bstride, const int *idx,
-                                                 const float *weight, float *grad_points, void *stream) {
+MGAR_API int mgar_three_interpolate_grad_batch_strided(int b, int c, int n, int m, const float *grad_out,
+                                                       long long grad_out_bstride, const int *idx,
+                                                       const float *weight, float *grad_points, void *stream) {
     MGAR_REQUIRE(b >= 0 && c >= 0 && m >= 0 && n >= 0, "three_interpolate_grad_batch: negative size");
     MGAR_REQUIRE(grad_out_bstride >= (long long)c * n, "three_interpolate_grad_batch: grad_out batch stride smaller than a sample");
     const size_t go_bs = (size_t)grad_out_bstride;
@@ -525,8 +525,8 @@ extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_gra
     }
     return check_launch("three_interpolate_grad_batch: launch failed");
 }
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_grad_batch(int b, int c, int n, int m, const float *grad_out, const int *idx,
-                                                 const float *weight, float *grad_points, void *stream) {
+MGAR_API int mgar_three_interpolate_grad_batch(int b, int c, int n, int m, const float *grad_out, const int *idx,
+                                               const float *weight, float *grad_points, void *stream) {
     return mgar_three_interpolate_grad_batch_strided(b, c, n, m, grad_out, (long long)c * n, idx, weight, grad_points, stream);
 }
 
@@ -541,17 +541,17 @@ static int three_interpolate_stack_impl(int N, int C, const T *features, const i
                        features, idx, weight, out);
     return check_launch("three_interpolate_stack: launch failed");
 }
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_stack(int N, int C, const float *features, const int *idx, const float *weight,
-                                            float *out, void *stream) {
+MGAR_API int mgar_three_interpolate_stack(int N, int C, const float *features, const int *idx, const float *weight,
+                                          float *out, void *stream) {
     return three_interpolate_stack_impl<float>(N, C, features, idx, weight, out, stream);
 }
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_stack_bf16(int N, int C, const void *features, const int *idx,
-                                            const float *weight, void *out, void *stream) {
+MGAR_API int mgar_three_interpolate_stack_bf16(int N, int C, const void *features, const int *idx,
+                                               const float *weight, void *out, void *stream) {
     return three_interpolate_stack_impl<bf16_t>(N, C, (const bf16_t *)features, idx, weight, (bf16_t *)out, stream);
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_grad_stack(int N, int C, const float *grad_out, const int *idx,
-                                                 const float *weight, float *grad_features, void *stream) {
+MGAR_API int mgar_three_interpolate_grad_stack(int N, int C, const float *grad_out, const int *idx,
+                                               const float *weight, float *grad_features, void *stream) {
     MGAR_REQUIRE(N >= 0 && C >= 0, "three_interpolate_grad_stack: negative size");
     const long long total = (long long)N * C;
     if (total == 0) return MGAR_OK;
@@ -575,11 +575,11 @@ static void launch_bwd_sorted(int b, int c, int n, int m, const float *grad_out,
                        (size_t)CH * n * sizeof(float), st, c, n, m, grad_out, go_bs, reinterpret_cast<const int2 *>(list), grad_points);
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_grad_sorted_batch_strided(int b, int c, int n, int m,
-                                                                                                       const float *grad_out,
-                                                                                                       long long grad_out_bstride,
-                                                                                                       const int *list,
-                                                                                                       float *grad_points, void *stream) {
+MGAR_API int mgar_three_interpolate_grad_sorted_batch_strided(int b, int c, int n, int m,
+                                                              const float *grad_out,
+                                                              long long grad_out_bstride,
+                                                              const int *list,
+                                                              float *grad_points, void *stream) {
     MGAR_REQUIRE(b >= 0 && c >= 0 && m >= 0 && n >= 0, "three_interpolate_grad_sorted_batch: negative size");
     MGAR_REQUIRE(grad_out_bstride >= (long long)c * n, "three_interpolate_grad_sorted_batch: grad_out batch stride smaller than a sample");
     MGAR_REQUIRE((n & 3) != 0 || (grad_out_bstride % 4 == 0 && (uintptr_t)grad_out % 16 == 0),
@@ -603,9 +603,9 @@ extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_gra
     else launch_bwd_sorted<1>(b, c, n, m, grad_out, go_bs, list, grad_points, st);
     return check_launch("three_interpolate_grad_sorted_batch: launch failed");
 }
-extern "C" __attribute__((visibility("default"))) int mgar_three_interpolate_grad_sorted_batch(int b, int c, int n, int m,
-                                                                                               const float *grad_out,
-                                                                                               const int *list,
-                                                                                               float *grad_points, void *stream) {
+MGAR_API int mgar_three_interpolate_grad_sorted_batch(int b, int c, int n, int m,
+                                                      const float *grad_out,
+                                                      const int *list,
+                                                      float *grad_points, void *stream) {
     return mgar_three_interpolate_grad_sorted_batch_strided(b, c, n, m, grad_out, (long long)c * n, list, grad_points, stream);
 }

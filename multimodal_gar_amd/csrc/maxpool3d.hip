@@ -145,13 +145,13 @@ static int maxpool3d_same_fwd_impl(const T_ *x, int NC, int T, int H, int W, int
     return check_launch("maxpool3d_same_fwd: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_maxpool3d_same_fwd(const float *x, int NC, int T, int H, int W, int kt, int kh,
-                                                                             int kw, int st, int sh, int sw, float *y, void *stream) {
+MGAR_API int mgar_maxpool3d_same_fwd(const float *x, int NC, int T, int H, int W, int kt, int kh,
+                                     int kw, int st, int sh, int sw, float *y, void *stream) {
     return maxpool3d_same_fwd_impl<float>(x, NC, T, H, W, kt, kh, kw, st, sh, sw, y, stream);
 }
-extern "C" __attribute__((visibility("default"))) int mgar_maxpool3d_same_fwd_bf16(const void *x, int NC, int T, int H, int W, int kt,
-                                                                                  int kh, int kw, int st, int sh, int sw, void *y,
-                                                                                  void *stream) {
+MGAR_API int mgar_maxpool3d_same_fwd_bf16(const void *x, int NC, int T, int H, int W, int kt,
+                                          int kh, int kw, int st, int sh, int sw, void *y,
+                                          void *stream) {
     return maxpool3d_same_fwd_impl<bf16_t>((const bf16_t *)x, NC, T, H, W, kt, kh, kw, st, sh, sw, (bf16_t *)y, stream);
 }
 
@@ -160,12 +160,12 @@ extern "C" __attribute__((visibility("default"))) int mgar_maxpool3d_same_fwd_bf
 // and max(., 0) are all monotone -- and relu(.) >= 0 makes the zero padding a no-op, so
 //     maxpool_same(relu(bn(x))) == relu(bn(maxpool_valid(x)))     bit for bit,
 // and the BatchNorm + ReLU pass runs over the pooled tensor (1/4 ... 1/8 of the elements) instead of the full one.
-extern "C" __attribute__((visibility("default"))) int mgar_maxpool3d_valid_fwd(const float *x, int NC, int T, int H, int W, int kt, int kh,
-                                                                              int kw, int st, int sh, int sw, float *y, void *stream) {
+MGAR_API int mgar_maxpool3d_valid_fwd(const float *x, int NC, int T, int H, int W, int kt, int kh,
+                                      int kw, int st, int sh, int sw, float *y, void *stream) {
     return maxpool3d_same_fwd_impl<float>(x, NC, T, H, W, kt, kh, kw, st, sh, sw, y, stream, 0);
 }
-extern "C" __attribute__((visibility("default"))) int mgar_maxpool3d_valid_fwd_bf16(const void *x, int NC, int T, int H, int W, int kt,
-                                                                                   int kh, int kw, int st, int sh, int sw, void *y,
-                                                                                   void *stream) {
+MGAR_API int mgar_maxpool3d_valid_fwd_bf16(const void *x, int NC, int T, int H, int W, int kt,
+                                           int kh, int kw, int st, int sh, int sw, void *y,
+                                           void *stream) {
     return maxpool3d_same_fwd_impl<bf16_t>((const bf16_t *)x, NC, T, H, W, kt, kh, kw, st, sh, sw, (bf16_t *)y, stream, 0);
 }

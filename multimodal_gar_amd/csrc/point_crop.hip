@@ -119,10 +119,8 @@ __global__ __launch_bounds__(PC_THREADS) void roipoint_pool3d_kernel(int pts_num
 
 using namespace mgar;
 
-#define PC_API extern "C" __attribute__((visibility("default")))
-
-PC_API int mgar_points_in_boxes(int batch_size, int boxes_num, int pts_num, const float *boxes, const float *pts,
-                                int *box_idx_of_points, void *stream) {
+MGAR_API int mgar_points_in_boxes(int batch_size, int boxes_num, int pts_num, const float *boxes, const float *pts,
+                                  int *box_idx_of_points, void *stream) {
     MGAR_REQUIRE(batch_size >= 0 && boxes_num >= 0 && pts_num >= 0, "points_in_boxes: negative size");
     if (boxes_num > PC_MAX_BOXES || batch_size > 65535) {
         set_error("points_in_boxes: at most 512 boxes per sample, 65535 samples");
@@ -137,9 +135,9 @@ PC_API int mgar_points_in_boxes(int batch_size, int boxes_num, int pts_num, cons
     return check_launch("points_in_boxes: launch failed");
 }
 
-PC_API int mgar_roipoint_pool3d_fwd(int batch_size, int pts_num, int boxes_num, int feature_in_len, int sampled_pts_num,
-                                    const float *xyz, const float *boxes3d, const float *pts_feature, float *pooled_features,
-                                    int *pooled_empty_flag, void *stream) {
+MGAR_API int mgar_roipoint_pool3d_fwd(int batch_size, int pts_num, int boxes_num, int feature_in_len, int sampled_pts_num,
+                                      const float *xyz, const float *boxes3d, const float *pts_feature, float *pooled_features,
+                                      int *pooled_empty_flag, void *stream) {
     MGAR_REQUIRE(batch_size >= 0 && pts_num >= 0 && boxes_num >= 0 && feature_in_len >= 0 && sampled_pts_num >= 1,
                  "roipoint_pool3d_fwd: bad sizes");
     if (sampled_pts_num > 32768 || batch_size > 65535) {

@@ -295,18 +295,18 @@ static void launch_dw(const float *x, const float *dy, int B, int Cin, int Cout,
 
 using namespace mgar;
 
-extern "C" __attribute__((visibility("default"))) int mgar_pointwise_dw_workspace_floats(int B, int Cin, int Cout, int P) {
+MGAR_API int mgar_pointwise_dw_workspace_floats(int B, int Cin, int Cout, int P) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || P <= 0) return 0;
     int ob, ib;
     dw_blocks(Cin, Cout, ob, ib);
     return dw_grid_x(B, Cin, Cout, P, ob, ib) * Cout * Cin;   // <= 2048 * 64 * 256
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_pointwise_conv_dw_act(const float *x, const float *dy, int B, int Cin,
-                                                                                int Cout, int P, const float *in_mean,
-                                                                                const float *in_invstd, const float *in_gamma,
-                                                                                const float *in_beta, int in_relu,
-                                                                                float *workspace, float *dw, void *stream) {
+MGAR_API int mgar_pointwise_conv_dw_act(const float *x, const float *dy, int B, int Cin,
+                                        int Cout, int P, const float *in_mean,
+                                        const float *in_invstd, const float *in_gamma,
+                                        const float *in_beta, int in_relu,
+                                        float *workspace, float *dw, void *stream) {
     MGAR_REQUIRE(B >= 0 && Cin >= 0 && Cout >= 0 && P >= 0, "pointwise_conv_dw: negative size");
     if (Cin == 0 || Cout == 0) return MGAR_OK;
     MGAR_REQUIRE(dw, "pointwise_conv_dw: null pointer");
@@ -334,9 +334,9 @@ extern "C" __attribute__((visibility("default"))) int mgar_pointwise_conv_dw_act
     return check_launch("pointwise_conv_dw: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_pointwise_conv_dw(const float *x, const float *dy, int B, int Cin,
-                                                                            int Cout, int P, float *workspace, float *dw,
-                                                                            void *stream) {
+MGAR_API int mgar_pointwise_conv_dw(const float *x, const float *dy, int B, int Cin,
+                                    int Cout, int P, float *workspace, float *dw,
+                                    void *stream) {
     return mgar_pointwise_conv_dw_act(x, dy, B, Cin, Cout, P, nullptr, nullptr, nullptr, nullptr, 0, workspace, dw, stream);
 }
 
@@ -345,18 +345,18 @@ extern "C" __attribute__((visibility("default"))) int mgar_pointwise_conv_dw(con
 // -> dw (Cout, Cin); dgamma, dbeta (Cin); coef (2 Cin) = {mean dz, mean dz xhat} for mgar_bn_act_bwd_apply[_rowmajor],
 // where dz = (W^T dy) [relu active].  Replaces mgar_pointwise_conv_dw_act + the reduction pass of mgar_bn_act_bwd over W^T dy
 // and x (8 * B * Cin * P bytes).  Cin <= 64, Cout <= 64.  workspace: mgar_pointwise_dw_bnbwd_workspace_floats(...) floats.
-extern "C" __attribute__((visibility("default"))) int mgar_pointwise_dw_bnbwd_workspace_floats(int B, int Cin, int Cout, int P) {
+MGAR_API int mgar_pointwise_dw_bnbwd_workspace_floats(int B, int Cin, int Cout, int P) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || P <= 0) return 0;
     int ob, ib;
     dw_blocks(2 * Cin, Cout, ob, ib);
     return dw_grid_x(B, 2 * Cin, Cout, P, ob, ib) * Cout * 2 * Cin + Cout * 2 * Cin;
 }
-extern "C" __attribute__((visibility("default"))) int mgar_pointwise_conv_dw_bnbwd(const float *x, const float *dy, const float *w, int B,
-                                                                                  int Cin, int Cout, int P, const float *in_mean,
-                                                                                  const float *in_invstd, const float *in_gamma,
-                                                                                  const float *in_beta, int in_relu, float *workspace,
-                                                                                  float *dw, float *dgamma, float *dbeta, float *coef,
-                                                                                  void *stream) {
+MGAR_API int mgar_pointwise_conv_dw_bnbwd(const float *x, const float *dy, const float *w, int B,
+                                          int Cin, int Cout, int P, const float *in_mean,
+                                          const float *in_invstd, const float *in_gamma,
+                                          const float *in_beta, int in_relu, float *workspace,
+                                          float *dw, float *dgamma, float *dbeta, float *coef,
+                                          void *stream) {
     MGAR_REQUIRE(B >= 0 && Cin >= 1 && Cout >= 1 && P >= 0, "pointwise_conv_dw_bnbwd: bad sizes");
     if (Cin > 64 || Cout > 64) {
         set_error("pointwise_conv_dw_bnbwd: Cin <= 64 and Cout <= 64");

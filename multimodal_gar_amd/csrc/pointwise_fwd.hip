@@ -220,17 +220,16 @@ static int pointwise_conv_fwd_impl(const T *x, int B, int Cin, int P, const floa
     return check_launch("pointwise_conv_fwd: launch failed");
 }
 
-#define PF_API extern "C" __attribute__((visibility("default")))
-PF_API int mgar_pointwise_conv_fwd(const float *x, int B, int Cin, int P, const float *w, int w_row_stride, int w_col_stride, int Cout,
-                                   const float *in_mean, const float *in_invstd, const float *in_gamma, const float *in_beta,
-                                   int in_relu, float *y, void *stream) {
+MGAR_API int mgar_pointwise_conv_fwd(const float *x, int B, int Cin, int P, const float *w, int w_row_stride, int w_col_stride, int Cout,
+                                     const float *in_mean, const float *in_invstd, const float *in_gamma, const float *in_beta,
+                                     int in_relu, float *y, void *stream) {
     return pointwise_conv_fwd_impl<float>(x, B, Cin, P, w, w_row_stride, w_col_stride, Cout, in_mean, in_invstd, in_gamma, in_beta,
                                           in_relu, y, stream);
 }
 // bf16 payload (x, y address bf16 elements; W and the BatchNorm vectors stay fp32)
-PF_API int mgar_pointwise_conv_fwd_bf16(const void *x, int B, int Cin, int P, const float *w, int w_row_stride, int w_col_stride,
-                                        int Cout, const float *in_mean, const float *in_invstd, const float *in_gamma,
-                                        const float *in_beta, int in_relu, void *y, void *stream) {
+MGAR_API int mgar_pointwise_conv_fwd_bf16(const void *x, int B, int Cin, int P, const float *w, int w_row_stride, int w_col_stride,
+                                          int Cout, const float *in_mean, const float *in_invstd, const float *in_gamma,
+                                          const float *in_beta, int in_relu, void *y, void *stream) {
     return pointwise_conv_fwd_impl<bf16_t>((const bf16_t *)x, B, Cin, P, w, w_row_stride, w_col_stride, Cout, in_mean, in_invstd,
                                            in_gamma, in_beta, in_relu, (bf16_t *)y, stream);
 }
@@ -238,9 +237,9 @@ PF_API int mgar_pointwise_conv_fwd_bf16(const void *x, int B, int Cin, int P, co
 // pointwise_conv_fwd that also leaves the BatchNorm statistics partials of its OUTPUT: out_stats (Cout, B * P / 128, 2) floats =
 // per (channel, 128-column tile) the tile's mean and sum of squared deviations, the chunk format mgar_bn_stats_from_partials
 // finalizes (chunk = 128).  P % 128 == 0, Cout <= 32.  fp32.  Saves the BatchNorm's own pass over y (4 * B * Cout * P bytes).
-PF_API int mgar_pointwise_conv_fwd_stats(const float *x, int B, int Cin, int P, const float *w, int w_row_stride, int w_col_stride,
-                                         int Cout, const float *in_mean, const float *in_invstd, const float *in_gamma,
-                                         const float *in_beta, int in_relu, float *y, float *out_stats, void *stream) {
+MGAR_API int mgar_pointwise_conv_fwd_stats(const float *x, int B, int Cin, int P, const float *w, int w_row_stride, int w_col_stride,
+                                           int Cout, const float *in_mean, const float *in_invstd, const float *in_gamma,
+                                           const float *in_beta, int in_relu, float *y, float *out_stats, void *stream) {
     MGAR_REQUIRE(out_stats, "pointwise_conv_fwd_stats: null pointer");
     if (Cout > 32) {
         set_error("pointwise_conv_fwd_stats: Cout <= 32 (run mgar_pointwise_conv_fwd and the BatchNorm's own statistics pass)");

@@ -985,8 +985,6 @@ constexpr int QG_LDS_MAX_FLOATS = 36864;
 
 using namespace mgar;
 
-#define QG_API extern "C" __attribute__((visibility("default")))
-
 template <typename T>
 static int qg_batch_fwd(int b, int c, int n, int npoints, int nsample, const float *xyz, const float *new_xyz,
                         const T *features, const float *wx, const int *idx, T *rel_out, size_t rel_bstride,
@@ -1029,31 +1027,31 @@ static int qg_batch_bwd(int b, int c, int n, int npoints, int nsample, const flo
     return check_launch(what);
 }
 
-QG_API int mgar_query_group_batch_fwd(int b, int c, int n, int npoints, int nsample, const float *xyz, const float *new_xyz,
-                                      const float *features, const int *idx, float *out, void *stream) {
+MGAR_API int mgar_query_group_batch_fwd(int b, int c, int n, int npoints, int nsample, const float *xyz, const float *new_xyz,
+                                        const float *features, const int *idx, float *out, void *stream) {
     const size_t cols = (size_t)npoints * nsample;
     return qg_batch_fwd<float>(b, c, n, npoints, nsample, xyz, new_xyz, features, nullptr, idx, out, (3 + c) * cols,
                                out ? out + 3 * cols : nullptr, (3 + c) * cols, stream, "query_group_batch_fwd: launch failed");
 }
 
-QG_API int mgar_query_group_batch_bwd(int b, int c, int n, int npoints, int nsample, const float *grad_out, const int *idx,
-                                      float *grad_features, void *stream) {
+MGAR_API int mgar_query_group_batch_bwd(int b, int c, int n, int npoints, int nsample, const float *grad_out, const int *idx,
+                                        float *grad_features, void *stream) {
     const size_t cols = (size_t)npoints * nsample;
     return qg_batch_bwd(b, c, n, npoints, nsample, grad_out ? grad_out + 3 * cols : nullptr, (3 + c) * cols, idx, grad_features,
                         stream, "query_group_batch_bwd: launch failed");
 }
 
-QG_API int mgar_query_group_proj_batch_fwd(int b, int c, int n, int npoints, int nsample, const float *xyz,
-                                           const float *new_xyz, const float *zf, const float *wx, const int *idx,
-                                           float *rel_out, float *y_out, void *stream) {
+MGAR_API int mgar_query_group_proj_batch_fwd(int b, int c, int n, int npoints, int nsample, const float *xyz,
+                                             const float *new_xyz, const float *zf, const float *wx, const int *idx,
+                                             float *rel_out, float *y_out, void *stream) {
     MGAR_REQUIRE(wx && zf && y_out, "query_group_proj_batch_fwd: null pointer");
     const size_t cols = (size_t)npoints * nsample;
     return qg_batch_fwd<float>(b, c, n, npoints, nsample, xyz, new_xyz, zf, wx, idx, rel_out, 3 * cols, y_out, (size_t)c * cols,
                                stream, "query_group_proj_batch_fwd: launch failed");
 }
 
-QG_API int mgar_query_group_proj_batch_bwd(int b, int c, int n, int npoints, int nsample, const float *grad_y, const int *idx,
-                                           float *grad_zf, void *stream) {
+MGAR_API int mgar_query_group_proj_batch_bwd(int b, int c, int n, int npoints, int nsample, const float *grad_y, const int *idx,
+                                             float *grad_zf, void *stream) {
     return qg_batch_bwd(b, c, n, npoints, nsample, grad_y, (size_t)c * npoints * nsample, idx, grad_zf, stream,
                         "query_group_proj_batch_bwd: launch failed");
 }
@@ -1086,23 +1084,23 @@ static int qg_stack_bwd(int B, int M, int C, int nsample, const float *grad_y, c
     return check_launch(what);
 }
 
-QG_API int mgar_query_group_stack_fwd(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
-                                      const float *new_xyz, const int *new_xyz_batch_cnt, const float *features, const int *idx,
-                                      float *out, void *stream) {
+MGAR_API int mgar_query_group_stack_fwd(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
+                                        const float *new_xyz, const int *new_xyz_batch_cnt, const float *features, const int *idx,
+                                        float *out, void *stream) {
     const size_t ms = (size_t)M * nsample;
     return qg_stack_fwd<float>(B, M, C, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features, C, nullptr, idx, out,
                                out ? out + 3 * ms : nullptr, stream, "query_group_stack_fwd: launch failed");
 }
 
-QG_API int mgar_query_group_stack_bwd(int B, int M, int C, int nsample, const float *grad_out, const int *idx,
-                                      const int *new_xyz_batch_cnt, const int *xyz_batch_cnt, float *grad_features, void *stream) {
+MGAR_API int mgar_query_group_stack_bwd(int B, int M, int C, int nsample, const float *grad_out, const int *idx,
+                                        const int *new_xyz_batch_cnt, const int *xyz_batch_cnt, float *grad_features, void *stream) {
     return qg_stack_bwd(B, M, C, nsample, grad_out ? grad_out + 3 * (size_t)M * nsample : nullptr, idx, new_xyz_batch_cnt,
                         xyz_batch_cnt, grad_features, C, stream, "query_group_stack_bwd: launch failed");
 }
 
-QG_API int mgar_query_group_proj_stack_fwd(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
-                                           const float *new_xyz, const int *new_xyz_batch_cnt, const float *zf, int zf_ld,
-                                           const float *wx, const int *idx, float *rel_out, float *y_out, void *stream) {
+MGAR_API int mgar_query_group_proj_stack_fwd(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
+                                             const float *new_xyz, const int *new_xyz_batch_cnt, const float *zf, int zf_ld,
+                                             const float *wx, const int *idx, float *rel_out, float *y_out, void *stream) {
     MGAR_REQUIRE(wx && zf && y_out && zf_ld >= C, "query_group_proj_stack_fwd: null pointer or zf_ld < C");
     return qg_stack_fwd<float>(B, M, C, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, zf, zf_ld, wx, idx, rel_out, y_out,
                                stream, "query_group_proj_stack_fwd: launch failed");
@@ -1111,50 +1109,50 @@ QG_API int mgar_query_group_proj_stack_fwd(int B, int M, int C, int nsample, con
 // The same, also leaving the BatchNorm statistics partials of y_out: out_stats (C, M * nsample / 128, 2) floats = per (channel,
 // 128-column tile) the tile's mean and sum of squared deviations (chunk format of mgar_bn_stats_from_partials, chunk = 128).
 // M * nsample % 128 == 0.  fp32.
-QG_API int mgar_query_group_proj_stack_fwd_stats(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
-                                                 const float *new_xyz, const int *new_xyz_batch_cnt, const float *zf, int zf_ld,
-                                                 const float *wx, const int *idx, float *rel_out, float *y_out, float *out_stats,
-                                                 void *stream) {
+MGAR_API int mgar_query_group_proj_stack_fwd_stats(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
+                                                   const float *new_xyz, const int *new_xyz_batch_cnt, const float *zf, int zf_ld,
+                                                   const float *wx, const int *idx, float *rel_out, float *y_out, float *out_stats,
+                                                   void *stream) {
     MGAR_REQUIRE(wx && zf && y_out && out_stats && zf_ld >= C, "query_group_proj_stack_fwd_stats: null pointer or zf_ld < C");
     return qg_stack_fwd<float>(B, M, C, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, zf, zf_ld, wx, idx, rel_out, y_out,
                                stream, "query_group_proj_stack_fwd_stats: launch failed", out_stats);
 }
 
-QG_API int mgar_query_group_proj_stack_bwd(int B, int M, int C, int nsample, const float *grad_y, const int *idx,
-                                           const int *new_xyz_batch_cnt, const int *xyz_batch_cnt, float *grad_zf, int zf_ld,
-                                           void *stream) {
+MGAR_API int mgar_query_group_proj_stack_bwd(int B, int M, int C, int nsample, const float *grad_y, const int *idx,
+                                             const int *new_xyz_batch_cnt, const int *xyz_batch_cnt, float *grad_zf, int zf_ld,
+                                             void *stream) {
     return qg_stack_bwd(B, M, C, nsample, grad_y, idx, new_xyz_batch_cnt, xyz_batch_cnt, grad_zf, zf_ld, stream,
                         "query_group_proj_stack_bwd: launch failed");
 }
 
 // ---- bf16 payload twins of the forward entry points: features / zf / out / rel_out / y_out address bf16 elements; xyz, new_xyz,
 // wx and every index stay fp32 / int32 (index parity must not depend on the payload type) ----
-QG_API int mgar_query_group_batch_fwd_bf16(int b, int c, int n, int npoints, int nsample, const float *xyz, const float *new_xyz,
-                                           const void *features, const int *idx, void *out, void *stream) {
+MGAR_API int mgar_query_group_batch_fwd_bf16(int b, int c, int n, int npoints, int nsample, const float *xyz, const float *new_xyz,
+                                             const void *features, const int *idx, void *out, void *stream) {
     const size_t cols = (size_t)npoints * nsample;
     bf16_t *o = (bf16_t *)out;
     return qg_batch_fwd<bf16_t>(b, c, n, npoints, nsample, xyz, new_xyz, (const bf16_t *)features, nullptr, idx, o, (3 + c) * cols,
                                 o ? o + 3 * cols : nullptr, (3 + c) * cols, stream, "query_group_batch_fwd_bf16: launch failed");
 }
-QG_API int mgar_query_group_proj_batch_fwd_bf16(int b, int c, int n, int npoints, int nsample, const float *xyz,
-                                                const float *new_xyz, const void *zf, const float *wx, const int *idx,
-                                                void *rel_out, void *y_out, void *stream) {
+MGAR_API int mgar_query_group_proj_batch_fwd_bf16(int b, int c, int n, int npoints, int nsample, const float *xyz,
+                                                  const float *new_xyz, const void *zf, const float *wx, const int *idx,
+                                                  void *rel_out, void *y_out, void *stream) {
     MGAR_REQUIRE(wx && zf && y_out, "query_group_proj_batch_fwd_bf16: null pointer");
     const size_t cols = (size_t)npoints * nsample;
     return qg_batch_fwd<bf16_t>(b, c, n, npoints, nsample, xyz, new_xyz, (const bf16_t *)zf, wx, idx, (bf16_t *)rel_out, 3 * cols,
                                 (bf16_t *)y_out, (size_t)c * cols, stream, "query_group_proj_batch_fwd_bf16: launch failed");
 }
-QG_API int mgar_query_group_stack_fwd_bf16(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
-                                           const float *new_xyz, const int *new_xyz_batch_cnt, const void *features,
-                                           const int *idx, void *out, void *stream) {
+MGAR_API int mgar_query_group_stack_fwd_bf16(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
+                                             const float *new_xyz, const int *new_xyz_batch_cnt, const void *features,
+                                             const int *idx, void *out, void *stream) {
     const size_t ms = (size_t)M * nsample;
     bf16_t *o = (bf16_t *)out;
     return qg_stack_fwd<bf16_t>(B, M, C, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, (const bf16_t *)features, C, nullptr,
                                 idx, o, o ? o + 3 * ms : nullptr, stream, "query_group_stack_fwd_bf16: launch failed");
 }
-QG_API int mgar_query_group_proj_stack_fwd_bf16(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
-                                                const float *new_xyz, const int *new_xyz_batch_cnt, const void *zf, int zf_ld,
-                                                const float *wx, const int *idx, void *rel_out, void *y_out, void *stream) {
+MGAR_API int mgar_query_group_proj_stack_fwd_bf16(int B, int M, int C, int nsample, const float *xyz, const int *xyz_batch_cnt,
+                                                  const float *new_xyz, const int *new_xyz_batch_cnt, const void *zf, int zf_ld,
+                                                  const float *wx, const int *idx, void *rel_out, void *y_out, void *stream) {
     MGAR_REQUIRE(wx && zf && y_out && zf_ld >= C, "query_group_proj_stack_fwd_bf16: null pointer or zf_ld < C");
     return qg_stack_fwd<bf16_t>(B, M, C, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, (const bf16_t *)zf, zf_ld, wx, idx,
                                 (bf16_t *)rel_out, (bf16_t *)y_out, stream, "query_group_proj_stack_fwd_bf16: launch failed");
@@ -1162,7 +1160,7 @@ QG_API int mgar_query_group_proj_stack_fwd_bf16(int B, int M, int C, int nsample
 
 // ---- stack backward without atomics: see qg_inv_index_kernel / qg_stack_bwd_rows_kernel ------------------------------------------
 // Capacity (in items of 4 ints) of the work-item array for B samples, N source rows, total = M * nsample columns.
-QG_API long long mgar_query_group_stack_inverse_items(int B, int N, long long total) {
+MGAR_API long long mgar_query_group_stack_inverse_items(int B, int N, long long total) {
     if (B < 0 || N < 0 || total < 0) return -1;
     return (long long)N + total / QR_PART + (N + QW_ROWS - 1) / QW_ROWS + B + 1;
 }
@@ -1170,16 +1168,16 @@ QG_API long long mgar_query_group_stack_inverse_items(int B, int N, long long to
 // list slot, table entry and per-run offsets, the rows cut into several items, and the window-split copy of the columns.
 // The first 2 + total / QR_PART + 1 ints (head, multi_rows) are read again by mgar_query_group_stack_bwd_rows.
 static long long qi_nwin_ub(int B, int N) { return (long long)(N + QW_ROWS - 1) / QW_ROWS + B; }
-QG_API long long mgar_query_group_stack_inverse_workspace_ints(int B, int N, long long total) {
+MGAR_API long long mgar_query_group_stack_inverse_workspace_ints(int B, int N, long long total) {
     if (B < 0 || N < 0 || total < 0) return -1;
     return 4 + (total / QR_PART + 1) + qi_nwin_ub(B, N) * (1 + 4 + QP_RUNS) + 2 * total + 4;
 }
 // idx: raw ball-query result (M, nsample).  list (M*nsample ints), items (capacity above, ZERO-FILLED by the caller), row_item (N),
 // workspace (size above).  No sample may hold more than QP_WINDOWS * QW_ROWS = 262 144 source rows (not checked: the counts
 // live on the device) -- the caller guarantees it.
-QG_API int mgar_query_group_stack_inverse_index(int B, int M, int nsample, int N, const int *idx, const int *new_xyz_batch_cnt,
-                                                const int *xyz_batch_cnt, int *workspace, int *list, int *items, int *row_item,
-                                                void *stream) {
+MGAR_API int mgar_query_group_stack_inverse_index(int B, int M, int nsample, int N, const int *idx, const int *new_xyz_batch_cnt,
+                                                  const int *xyz_batch_cnt, int *workspace, int *list, int *items, int *row_item,
+                                                  void *stream) {
     MGAR_REQUIRE(B >= 0 && M >= 0 && nsample >= 1 && N >= 0, "query_group_stack_inverse_index: bad sizes");
     MGAR_REQUIRE((long long)M * nsample < (1ll << 31) - 64 * QW_LOADS, "query_group_stack_inverse_index: M * nsample >= 2^31");
     MGAR_REQUIRE(B <= 65535, "query_group_stack_inverse_index: B > 65535");
@@ -1207,10 +1205,10 @@ QG_API int mgar_query_group_stack_inverse_index(int B, int M, int nsample, int N
 // g_t: ROW-MAJOR gradient (M*nsample, C), C <= 64.  grad_zf (N, ld): rows with references are written, the others left alone.
 // workspace: the index's (its head and multi-part row list).  part_rows: n_items * C floats of scratch.  wx_part: ceil(n_items / 8) * C * 3 floats, ZERO-FILLED by the caller: its sum over the
 // first axis is d wx (C, 3) = sum_col g_t[col] (x) (xyz[row] - new_xyz[col / nsample]); NULL (with xyz, new_xyz) to skip it.
-QG_API int mgar_query_group_stack_bwd_rows(int n_items, int N, int C, int nsample, const int *workspace, const int *items,
-                                           const int *row_item, const int *list, const float *g_t, const float *xyz,
-                                           const float *new_xyz, float *grad_zf, int ld, float *part_rows, float *wx_part,
-                                           long long total, void *stream) {
+MGAR_API int mgar_query_group_stack_bwd_rows(int n_items, int N, int C, int nsample, const int *workspace, const int *items,
+                                             const int *row_item, const int *list, const float *g_t, const float *xyz,
+                                             const float *new_xyz, float *grad_zf, int ld, float *part_rows, float *wx_part,
+                                             long long total, void *stream) {
     MGAR_REQUIRE(n_items >= 0 && N >= 0 && C >= 1 && ld >= C && nsample >= 1 && total >= 0, "query_group_stack_bwd_rows: bad sizes");
     if (C > 64) {
         set_error("query_group_stack_bwd_rows: C <= 64");

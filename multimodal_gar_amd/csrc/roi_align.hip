@@ -137,28 +137,28 @@ static int roi_align_fwd_impl(const T *input, int N, int C, int H, int W, const 
                        pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned, out);
     return check_launch("roi_align_fwd: launch failed");
 }
-extern "C" __attribute__((visibility("default"))) int mgar_roi_align_fwd(const float *input, int N, int C, int H, int W,
-                                                                        const float *rois, int K, int pooled_h,
-                                                                        int pooled_w, float spatial_scale,
-                                                                        int sampling_ratio, int aligned, float *out,
-                                                                        void *stream) {
+MGAR_API int mgar_roi_align_fwd(const float *input, int N, int C, int H, int W,
+                                const float *rois, int K, int pooled_h,
+                                int pooled_w, float spatial_scale,
+                                int sampling_ratio, int aligned, float *out,
+                                void *stream) {
     return roi_align_fwd_impl<float>(input, N, C, H, W, rois, K, pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned, out, stream);
 }
 // bf16 payload: input / out address bf16 elements, rois stay fp32
-extern "C" __attribute__((visibility("default"))) int mgar_roi_align_fwd_bf16(const void *input, int N, int C, int H, int W,
-                                                                             const float *rois, int K, int pooled_h,
-                                                                             int pooled_w, float spatial_scale,
-                                                                             int sampling_ratio, int aligned, void *out,
-                                                                             void *stream) {
+MGAR_API int mgar_roi_align_fwd_bf16(const void *input, int N, int C, int H, int W,
+                                     const float *rois, int K, int pooled_h,
+                                     int pooled_w, float spatial_scale,
+                                     int sampling_ratio, int aligned, void *out,
+                                     void *stream) {
     return roi_align_fwd_impl<bf16_t>((const bf16_t *)input, N, C, H, W, rois, K, pooled_h, pooled_w, spatial_scale, sampling_ratio,
                                       aligned, (bf16_t *)out, stream);
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_roi_align_bwd(const float *grad_out, int N, int C, int H, int W,
-                                                                        const float *rois, int K, int pooled_h,
-                                                                        int pooled_w, float spatial_scale,
-                                                                        int sampling_ratio, int aligned,
-                                                                        float *grad_input, void *stream) {
+MGAR_API int mgar_roi_align_bwd(const float *grad_out, int N, int C, int H, int W,
+                                const float *rois, int K, int pooled_h,
+                                int pooled_w, float spatial_scale,
+                                int sampling_ratio, int aligned,
+                                float *grad_input, void *stream) {
     MGAR_REQUIRE(roi_args_ok(N, C, H, W, K, pooled_h, pooled_w), "roi_align_bwd: bad sizes");
     const long long total = (long long)K * C * pooled_h * pooled_w;
     if (total == 0) return MGAR_OK;

@@ -133,13 +133,13 @@ static void launch_rd(const float *A, int lda, const float *F, int ldf, long lon
 
 using namespace mgar;
 
-extern "C" __attribute__((visibility("default"))) int mgar_rowmajor_dw_workspace_floats(long long N, int Co, int Ci) {
+MGAR_API int mgar_rowmajor_dw_workspace_floats(long long N, int Co, int Ci) {
     if (N <= 0 || Co <= 0 || Ci <= 0) return 0;
     return rd_workgroups(N) * 4 * Co * Ci;
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_rowmajor_dw(const float *a, int lda, const float *f, int ldf, long long N,
-                                                                      int Co, int Ci, float *workspace, float *dw, void *stream) {
+MGAR_API int mgar_rowmajor_dw(const float *a, int lda, const float *f, int ldf, long long N,
+                              int Co, int Ci, float *workspace, float *dw, void *stream) {
     MGAR_REQUIRE(N >= 0 && Co >= 0 && Ci >= 0 && lda >= Co && ldf >= Ci, "rowmajor_dw: bad sizes");
     if (Co == 0 || Ci == 0) return MGAR_OK;
     MGAR_REQUIRE(dw, "rowmajor_dw: null pointer");

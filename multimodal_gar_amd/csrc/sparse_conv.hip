@@ -717,16 +717,14 @@ __global__ __launch_bounds__(256) void sp_pairs_fill_kernel(int No, int K, const
 
 using namespace mgar;
 
-#define SP_API extern "C" __attribute__((visibility("default")))
-
 static int g_spconv_os = 1;
 // A/B switch (tests, profiles): 1 = register-gather kernel where it applies (default), 0 = always the LDS kernel
-SP_API int mgar_spconv_set_register_gather(int on) { g_spconv_os = on ? 1 : 0; return MGAR_OK; }
+MGAR_API int mgar_spconv_set_register_gather(int on) { g_spconv_os = on ? 1 : 0; return MGAR_OK; }
 
 // Hash table over the voxel coordinates coords (N, 4) int32 [b, z, y, x] of a (Z, Y, X) grid.  table_keys (capacity) int64
 // must be pre-filled with -1 and table_vals (capacity) int32 with INT_MAX by the caller; capacity a power of two >= 2 N.
-SP_API int mgar_voxel_hash_build(int N, const int *coords, int Z, int Y, int X, long long *table_keys, int *table_vals,
-                                 int capacity, void *stream) {
+MGAR_API int mgar_voxel_hash_build(int N, const int *coords, int Z, int Y, int X, long long *table_keys, int *table_vals,
+                                   int capacity, void *stream) {
     MGAR_REQUIRE(N >= 0 && Z > 0 && Y > 0 && X > 0 && capacity > 0 && (capacity & (capacity - 1)) == 0 && capacity >= 2 * N,
                  "voxel_hash_build: capacity must be a power of two >= 2 N");
     if (N == 0) return MGAR_OK;
@@ -739,8 +737,8 @@ SP_API int mgar_voxel_hash_build(int N, const int *coords, int Z, int Y, int X, 
 
 // rows[i] = row id stored for coords[i] (M, 4), or -1 (the sparse replacement of indexing the dense (B, Z, Y, X) table of
 // pcdet/utils/common_utils.py:244-252)
-SP_API int mgar_voxel_hash_lookup(int M, const int *coords, int Z, int Y, int X, const long long *table_keys, const int *table_vals,
-                                  int capacity, int *rows, void *stream) {
+MGAR_API int mgar_voxel_hash_lookup(int M, const int *coords, int Z, int Y, int X, const long long *table_keys, const int *table_vals,
+                                    int capacity, int *rows, void *stream) {
     MGAR_REQUIRE(M >= 0 && Z > 0 && Y > 0 && X > 0 && capacity > 0 && (capacity & (capacity - 1)) == 0, "voxel_hash_lookup: bad sizes");
     if (M == 0) return MGAR_OK;
     MGAR_REQUIRE(coords && table_keys && table_vals && rows, "voxel_hash_lookup: null pointer");
@@ -754,8 +752,8 @@ SP_API int mgar_voxel_hash_lookup(int M, const int *coords, int Z, int Y, int X,
 //   inverse = 0: site_coords = OUTPUT sites (No, 4), table = hash of the INPUT sites -> nbr (No, K): input row under offset k
 //   inverse = 1: site_coords = INPUT sites (Ni, 4), table = hash of the OUTPUT sites -> nbr (Ni, K): output row reached through k
 // K = kz * ky * kx, offsets ordered z-major (k = (kz * KY + ky) * KX + kx, the order of spconv's (O, kd, kh, kw, I) weight).
-SP_API int mgar_spconv_rulebook(int n_sites, const int *site_coords, const int *geom, const long long *table_keys,
-                                const int *table_vals, int capacity, int inverse, int *nbr, void *stream) {
+MGAR_API int mgar_spconv_rulebook(int n_sites, const int *site_coords, const int *geom, const long long *table_keys,
+                                  const int *table_vals, int capacity, int inverse, int *nbr, void *stream) {
     MGAR_REQUIRE(n_sites >= 0 && geom && sp_geom_ok(geom) && capacity > 0 && (capacity & (capacity - 1)) == 0, "spconv_rulebook: bad geometry");
     if (n_sites == 0) return MGAR_OK;
     MGAR_REQUIRE(site_coords && table_keys && table_vals && nbr, "spconv_rulebook: null pointer");
@@ -775,7 +773,7 @@ SP_API int mgar_spconv_rulebook(int n_sites, const int *site_coords, const int *
 }
 
 // keys (n_in, K) int64: see sp_output_keys_kernel.  geom as in mgar_spconv_rulebook.
-SP_API int mgar_spconv_output_keys(int n_in, const int *in_coords, const int *geom, long long *keys, void *stream) {
+MGAR_API int mgar_spconv_output_keys(int n_in, const int *in_coords, const int *geom, long long *keys, void *stream) {
     MGAR_REQUIRE(n_in >= 0 && geom && sp_geom_ok(geom), "spconv_output_keys: bad geometry");
     if (n_in == 0) return MGAR_OK;
     MGAR_REQUIRE(in_coords && keys, "spconv_output_keys: null pointer");
@@ -792,8 +790,8 @@ SP_API int mgar_spconv_output_keys(int n_in, const int *in_coords, const int *ge
 // out (No, Cout) = sum_k in[nbr[:, k]] . w[k]   with w (K, Cin, Cout) row-major; rows with nbr == -1 contribute nothing.
 // flip_k != 0 reads w[K - 1 - k] (data gradient of a submanifold convolution: its inverse rulebook is the forward one
 // with the offsets mirrored).  out is fully written.  Cin, Cout <= 128.
-SP_API int mgar_spconv_gather_gemm(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *w, int flip_k,
-                                   float *out, void *stream) {
+MGAR_API int mgar_spconv_gather_gemm(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *w, int flip_k,
+                                     float *out, void *stream) {
     MGAR_REQUIRE(No >= 0 && K >= 1 && K <= 343 && Cin >= 1 && Cout >= 1, "spconv_gather_gemm: bad sizes");
     if (Cin > SC_MAXC || Cout > SC_MAXC) {
         set_error("spconv_gather_gemm: C_in, C_out <= 128");
@@ -842,9 +840,9 @@ SP_API int mgar_spconv_gather_gemm(int No, int K, int Cin, int Cout, const float
 }
 
 // weight gradient: partial (nchunk, K, Cin, Cout) with nchunk = mgar_spconv_dw_chunks(No); dW = partial.sum(0) (caller).
-SP_API int mgar_spconv_dw_chunks(int No) { return No < 0 ? MGAR_EINVAL : (No + SC_DW_CHUNK - 1) / SC_DW_CHUNK; }
-SP_API int mgar_spconv_dw(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *dout, float *partial,
-                          void *stream) {
+MGAR_API int mgar_spconv_dw_chunks(int No) { return No < 0 ? MGAR_EINVAL : (No + SC_DW_CHUNK - 1) / SC_DW_CHUNK; }
+MGAR_API int mgar_spconv_dw(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *dout, float *partial,
+                            void *stream) {
     MGAR_REQUIRE(No >= 0 && K >= 1 && K <= 65535 && Cin >= 1 && Cout >= 1 && (No + SC_DW_CHUNK - 1) / SC_DW_CHUNK <= 65535, "spconv_dw: bad sizes");
     if (Cin > SC_MAXC || Cout > SC_MAXC) {
         set_error("spconv_dw: C_in, C_out <= 128");
@@ -870,9 +868,9 @@ SP_API int mgar_spconv_dw(int No, int K, int Cin, int Cout, const float *in, con
 // mgar_spconv_pair_chunk() pairs each, grouped by offset in ascending order; item_start (K + 1): first item of every offset.
 // partial (n_items, Cin, Cout) scratch; dw (K, Cin, Cout) fully written.  C_in, C_out powers of two <= 128
 // (MGAR_EUNSUPPORTED otherwise: use mgar_spconv_dw).
-SP_API int mgar_spconv_pair_chunk(void) { return SC_PAIR_CHUNK; }
-SP_API int mgar_spconv_pairs_dw(int n_items, int K, int Cin, int Cout, const float *in, const float *dout, const int *pair_i,
-                                const int *pair_o, const int *items, const int *item_start, float *partial, float *dw, void *stream) {
+MGAR_API int mgar_spconv_pair_chunk(void) { return SC_PAIR_CHUNK; }
+MGAR_API int mgar_spconv_pairs_dw(int n_items, int K, int Cin, int Cout, const float *in, const float *dout, const int *pair_i,
+                                  const int *pair_o, const int *items, const int *item_start, float *partial, float *dw, void *stream) {
     MGAR_REQUIRE(n_items >= 0 && K >= 1 && K <= 65535 && Cin >= 1 && Cout >= 1, "spconv_pairs_dw: bad sizes");
     if (Cin > SC_MAXC || Cout > SC_MAXC || (Cin & (Cin - 1)) || (Cout & (Cout - 1))) {
         set_error("spconv_pairs_dw: C_in, C_out must be powers of two <= 128");
@@ -907,8 +905,8 @@ SP_API int mgar_spconv_pairs_dw(int n_items, int K, int Cin, int Cout, const flo
 // dst (n_dst, Cd) must be ZERO-FILLED by the caller; w (K, Cs, Cd) row-major; items / pair lists as for mgar_spconv_pairs_dw,
 // item_start_host: the (K + 1) item offsets as a HOST array.  Forward: src = in, pair_src = pair_i, pair_dst = pair_o, w = W;
 // data gradient: src = dout, pair_src = pair_o, pair_dst = pair_i, w = W_k^T.  C_s a power of two <= 128, C_d <= 128.
-SP_API int mgar_spconv_pairs_gemm(int K, int Cs, int Cd, const float *src, const int *pair_src, const int *pair_dst, const int *items,
-                                  const int *item_start_host, const float *w, float *dst, void *stream) {
+MGAR_API int mgar_spconv_pairs_gemm(int K, int Cs, int Cd, const float *src, const int *pair_src, const int *pair_dst, const int *items,
+                                    const int *item_start_host, const float *w, float *dst, void *stream) {
     MGAR_REQUIRE(K >= 1 && K <= 65535 && Cs >= 1 && Cd >= 1 && item_start_host, "spconv_pairs_gemm: bad arguments");
     if (Cs > SC_MAXC || Cd > SC_MAXC || (Cs & (Cs - 1))) {
         set_error("spconv_pairs_gemm: C_src must be a power of two, both <= 128");
@@ -946,8 +944,8 @@ SP_API int mgar_spconv_pairs_gemm(int K, int Cs, int Cd, const float *src, const
 // scanned per offset, and total (K) int32; nblk = mgar_spconv_pairs_blocks(No).  The caller reads `total` (the one host
 // synchronisation of a rulebook), forms offset_start (K) int64 = exclusive sums of total, allocates pair_i / pair_o (sum of total) and
 // calls step 2, mgar_spconv_pairs_fill: pairs of offset k at [offset_start[k], offset_start[k] + total[k]), ascending output row.
-SP_API int mgar_spconv_pairs_blocks(int No) { return No < 0 ? MGAR_EINVAL : (No + SP_PB - 1) / SP_PB; }
-SP_API int mgar_spconv_pairs_count(int No, int K, const int *nbr, int *blk, int *total, void *stream) {
+MGAR_API int mgar_spconv_pairs_blocks(int No) { return No < 0 ? MGAR_EINVAL : (No + SP_PB - 1) / SP_PB; }
+MGAR_API int mgar_spconv_pairs_count(int No, int K, const int *nbr, int *blk, int *total, void *stream) {
     MGAR_REQUIRE(No >= 0 && K >= 1 && K <= 4096, "spconv_pairs_count: bad sizes");
     MGAR_REQUIRE(total, "spconv_pairs_count: null pointer");
     hipStream_t st = (hipStream_t)stream;
@@ -962,8 +960,8 @@ SP_API int mgar_spconv_pairs_count(int No, int K, const int *nbr, int *blk, int 
     hipLaunchKernelGGL(sp_pairs_scan_kernel, dim3(K), dim3(1024), 0, st, nblk, blk, total);
     return check_launch("spconv_pairs_count: launch failed");
 }
-SP_API int mgar_spconv_pairs_fill(int No, int K, const int *nbr, const int *blk, const long long *offset_start, int *pair_i, int *pair_o,
-                                  void *stream) {
+MGAR_API int mgar_spconv_pairs_fill(int No, int K, const int *nbr, const int *blk, const long long *offset_start, int *pair_i, int *pair_o,
+                                    void *stream) {
     MGAR_REQUIRE(No >= 0 && K >= 1 && K <= 4096, "spconv_pairs_fill: bad sizes");
     if (No == 0) return MGAR_OK;
     MGAR_REQUIRE(nbr && blk && offset_start && pair_i && pair_o, "spconv_pairs_fill: null pointer");

@@ -506,16 +506,14 @@ static int stem_conv_impl(const T *x, int N, int Tn, int H, int W, const float *
 
 using namespace mgar;
 
-#define SCV_API extern "C" __attribute__((visibility("default")))
-
 // x (N, 3, T, H, W), w (64, 3, 7, 7, 7) -> y (N, 64, ceil(T/2), ceil(H/2), ceil(W/2)); w_packed: caller-allocated scratch of
 // mgar_stem_conv3d_workspace_floats() floats (the weights re-laid out for the kernel, rewritten on every call).
-SCV_API int mgar_stem_conv3d_workspace_floats(void) { return SCV_K * SCV_CIN * (SW_W_FLOATS > SCV_W_FLOATS ? SW_W_FLOATS : SCV_W_FLOATS); }
+MGAR_API int mgar_stem_conv3d_workspace_floats(void) { return SCV_K * SCV_CIN * (SW_W_FLOATS > SCV_W_FLOATS ? SW_W_FLOATS : SCV_W_FLOATS); }
 // A/B switch (tests, tools): 0 = the direct kernel for fp32 too; default 1 = minimal filtering along W where W % 4 == 0
-SCV_API int mgar_stem_conv3d_set_minimal_filtering(int on) { g_stem_minimal_filtering = on ? 1 : 0; return MGAR_OK; }
-SCV_API int mgar_stem_conv3d_fwd(const float *x, int N, int T, int H, int W, const float *w, float *w_packed, float *y, void *stream) {
+MGAR_API int mgar_stem_conv3d_set_minimal_filtering(int on) { g_stem_minimal_filtering = on ? 1 : 0; return MGAR_OK; }
+MGAR_API int mgar_stem_conv3d_fwd(const float *x, int N, int T, int H, int W, const float *w, float *w_packed, float *y, void *stream) {
     return stem_conv_impl<float>(x, N, T, H, W, w, w_packed, y, stream);
 }
-SCV_API int mgar_stem_conv3d_fwd_bf16(const void *x, int N, int T, int H, int W, const float *w, float *w_packed, void *y, void *stream) {
+MGAR_API int mgar_stem_conv3d_fwd_bf16(const void *x, int N, int T, int H, int W, const float *w, float *w_packed, void *y, void *stream) {
     return stem_conv_impl<bf16_t>((const bf16_t *)x, N, T, H, W, w, w_packed, (bf16_t *)y, stream);
 }

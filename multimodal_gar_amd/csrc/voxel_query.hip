@@ -138,19 +138,19 @@ static int voxel_query_launch(bool hash, int M, int R1, int R2, int R3, int nsam
     return check_launch("voxel_query: launch failed");
 }
 
-extern "C" __attribute__((visibility("default"))) int mgar_voxel_query_stack(int M, int R1, int R2, int R3, int nsample, float radius, int z_range,
-                                      int y_range, int x_range, const float *new_xyz, const float *xyz,
-                                      const int *new_coords, const int *point_indices, int *idx, void *stream) {
+MGAR_API int mgar_voxel_query_stack(int M, int R1, int R2, int R3, int nsample, float radius, int z_range,
+                                    int y_range, int x_range, const float *new_xyz, const float *xyz,
+                                    const int *new_coords, const int *point_indices, int *idx, void *stream) {
     return voxel_query_launch(false, M, R1, R2, R3, nsample, radius, z_range, y_range, x_range, new_xyz, xyz, new_coords, point_indices,
                               nullptr, nullptr, 0, idx, stream);
 }
 
 // The same query with the voxel -> row lookups served by the hash table of mgar_voxel_hash_build instead of the dense
 // (B, R1, R2, R3) table: identical results (tests/test_sparse_conv_gpu.py), O(active voxels) memory.
-extern "C" __attribute__((visibility("default"))) int mgar_voxel_query_hash_stack(int M, int R1, int R2, int R3, int nsample, float radius,
-                                      int z_range, int y_range, int x_range, const float *new_xyz, const float *xyz,
-                                      const int *new_coords, const long long *table_keys, const int *table_vals, int capacity,
-                                      int *idx, void *stream) {
+MGAR_API int mgar_voxel_query_hash_stack(int M, int R1, int R2, int R3, int nsample, float radius,
+                                         int z_range, int y_range, int x_range, const float *new_xyz, const float *xyz,
+                                         const int *new_coords, const long long *table_keys, const int *table_vals, int capacity,
+                                         int *idx, void *stream) {
     return voxel_query_launch(true, M, R1, R2, R3, nsample, radius, z_range, y_range, x_range, new_xyz, xyz, new_coords, nullptr,
                               table_keys, table_vals, capacity, idx, stream);
 }

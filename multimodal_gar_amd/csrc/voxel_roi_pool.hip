@@ -261,22 +261,20 @@ static int vrp_moment_blocks(long long total) {
 
 using namespace mgar;
 
-#define VP_API extern "C" __attribute__((visibility("default")))
-
 // workspace sizes: doubles for the statistics pass, floats for the backward
-VP_API long long mgar_voxel_roi_pool_stats_workspace_doubles(int M, int nsample) {
+MGAR_API long long mgar_voxel_roi_pool_stats_workspace_doubles(int M, int nsample) {
     if (M < 0 || nsample < 0) return MGAR_EINVAL;
     return (long long)vrp_moment_blocks((long long)M * nsample) * 9;
 }
-VP_API long long mgar_voxel_roi_pool_bwd_workspace_floats(int M, int C) {
+MGAR_API long long mgar_voxel_roi_pool_bwd_workspace_floats(int M, int C) {
     if (M < 0 || C < 0) return MGAR_EINVAL;
     return (long long)vrp_blocks(M) * C * 5;
 }
 
-VP_API int mgar_voxel_roi_pool_stats(int M, int nsample, int C, const float *xyz, const float *new_xyz, const int *idx,
-                                     const float *w_pos, float eps, float momentum, double *workspace, double *moments, float *mean,
-                                     float *invstd, float *running_mean, float *running_var, long long *num_batches_tracked,
-                                     void *stream) {
+MGAR_API int mgar_voxel_roi_pool_stats(int M, int nsample, int C, const float *xyz, const float *new_xyz, const int *idx,
+                                       const float *w_pos, float eps, float momentum, double *workspace, double *moments, float *mean,
+                                       float *invstd, float *running_mean, float *running_var, long long *num_batches_tracked,
+                                       void *stream) {
     MGAR_REQUIRE(M >= 0 && nsample >= 1 && C >= 1 && C <= VP_MAXC, "voxel_roi_pool_stats: bad sizes (1 <= C <= 32)");
     if (M == 0) return MGAR_OK;
     MGAR_REQUIRE(xyz && new_xyz && idx && w_pos && workspace && moments && mean && invstd, "voxel_roi_pool_stats: null pointer");
@@ -305,23 +303,23 @@ static int vrp_fwd_impl(int M, int nsample, int C, const float *xyz, const float
     return check_launch("voxel_roi_pool_fwd: launch failed");
 }
 
-VP_API int mgar_voxel_roi_pool_fwd(int M, int nsample, int C, const float *xyz, const float *new_xyz, const float *feats, int ld_f,
-                                   const int *idx, const float *w_pos, const float *mean, const float *invstd, const float *gamma,
-                                   const float *beta, float *pooled, unsigned char *arg, void *stream) {
+MGAR_API int mgar_voxel_roi_pool_fwd(int M, int nsample, int C, const float *xyz, const float *new_xyz, const float *feats, int ld_f,
+                                     const int *idx, const float *w_pos, const float *mean, const float *invstd, const float *gamma,
+                                     const float *beta, float *pooled, unsigned char *arg, void *stream) {
     return vrp_fwd_impl<float>(M, nsample, C, xyz, new_xyz, feats, ld_f, idx, w_pos, mean, invstd, gamma, beta, pooled, arg, stream);
 }
-VP_API int mgar_voxel_roi_pool_fwd_bf16(int M, int nsample, int C, const float *xyz, const float *new_xyz, const void *feats, int ld_f,
-                                        const int *idx, const float *w_pos, const float *mean, const float *invstd,
-                                        const float *gamma, const float *beta, void *pooled, unsigned char *arg, void *stream) {
+MGAR_API int mgar_voxel_roi_pool_fwd_bf16(int M, int nsample, int C, const float *xyz, const float *new_xyz, const void *feats, int ld_f,
+                                          const int *idx, const float *w_pos, const float *mean, const float *invstd,
+                                          const float *gamma, const float *beta, void *pooled, unsigned char *arg, void *stream) {
     return vrp_fwd_impl<bf16_t>(M, nsample, C, xyz, new_xyz, (const bf16_t *)feats, ld_f, idx, w_pos, mean, invstd, gamma, beta,
                                 (bf16_t *)pooled, arg, stream);
 }
 
-VP_API int mgar_voxel_roi_pool_bwd(int M, int nsample, int C, const float *xyz, const float *new_xyz, const int *idx,
-                                   const float *w_pos, const float *mean, const float *invstd, const float *gamma,
-                                   const double *moments, int train_stats, const float *dpooled, const float *pooled,
-                                   const unsigned char *arg, float *workspace, float *dfeats, int ld_f, float *dgamma, float *dbeta,
-                                   float *dw_pos, void *stream) {
+MGAR_API int mgar_voxel_roi_pool_bwd(int M, int nsample, int C, const float *xyz, const float *new_xyz, const int *idx,
+                                     const float *w_pos, const float *mean, const float *invstd, const float *gamma,
+                                     const double *moments, int train_stats, const float *dpooled, const float *pooled,
+                                     const unsigned char *arg, float *workspace, float *dfeats, int ld_f, float *dgamma, float *dbeta,
+                                     float *dw_pos, void *stream) {
     MGAR_REQUIRE(M >= 0 && nsample >= 1 && C >= 1 && C <= VP_MAXC && (dfeats == nullptr || ld_f >= C), "voxel_roi_pool_bwd: bad sizes");
     if (M == 0) return MGAR_OK;
     MGAR_REQUIRE(xyz && new_xyz && idx && w_pos && mean && invstd && dpooled && pooled && arg && workspace && dw_pos &&

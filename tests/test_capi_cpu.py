@@ -41,12 +41,83 @@ def test_binding_return_types_match_the_header():
     from multimodal_gar_amd import _lib
     text = open(os.path.join(ROOT, "include", "mgar_ops.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    decl = dict((name, ret) for ret, name in re.findall(r"^\s*(long long|int)\s+(mgar_[a-z0-9_]+)\s*\(", text, flags=re.M))
+    decl = dict((name, ret) for ret, name in
+                re.findall(r"^\s*(long long|int|const char \*)\s*(mgar_[a-z0-9_]+)\s*\(", text, flags=re.M))
     assert len(decl) > 100
+    want = {"long long": ctypes.c_longlong, "int": ctypes.c_int, "const char *": ctypes.c_char_p}
     for name, fn in _lib._fns.items():
-        want = ctypes.c_longlong if decl[name] == "long long" else ctypes.c_int
-        assert fn.restype is want, name
-    assert _lib._LONGLONG_RESULTS == {n for n, r in decl.items() if r == "long long" and n in _lib._fns}
+        assert fn.restype is want[decl[name]], name
+    assert {n for n, f in _lib._fns.items() if f.restype is ctypes.c_longlong} == {n for n, r in decl.items() if r == "long long"}
+
+
+def test_binding_argument_types_match_the_header():
+    """argtypes per entry point against expectations written out by hand from include/mgar_ops.h: every scalar type of the
+    ABI and its awkward shapes.  An int where the header says long long (strides, totals) or a float for a double
+    truncates silently; nothing else would notice before wrong numbers on a GPU."""
+    from multimodal_gar_amd import _lib
+    I, F, D, LL, P, S = (ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p,
+                         ctypes.c_char_p)
+    interp_into = (I, [I, I, I, I, P, P, P, P, LL, P])
+    expect = {
+        "mgar_ktimer_add_flops": (I, [I, D]),
+        "mgar_ktimer_read": (I, [I, P, P, P, P, I]),
+        "mgar_ktimer_name": (S, [I]),
+        "mgar_last_error": (S, []),
+        "mgar_abi_version": (I, []),
+        "mgar_spconv_pair_chunk": (I, []),
+        "mgar_point_grid_workspace_bytes": (LL, [I, LL]),
+        "mgar_rowmajor_dw_workspace_floats": (I, [LL, I, I]),
+        "mgar_ball_query_batch": (I, [I, I, I, F, I, P, P, P, P]),
+        # host arrays radii / nsamples, then new_xyz, xyz, `int *const *idx`, stream
+        "mgar_ball_query_multi_batch": (I, [I, I, I, I, P, P, P, P, P, P]),
+        # dpool, three long long strides, then pointers and sizes
+        "mgar_bn_act_maxpool_bwd_strided": (I, [P, LL, LL, LL, P, P, P, P, I, I, I, I, P, P, P, I, P, P, P, P, P]),
+        "mgar_three_interpolate_batch_into": interp_into,
+        "mgar_three_interpolate_batch_into_bf16": interp_into,
+        "mgar_image_resize_normalize_u8": (I, [I, I, I, I, I, P, P, P, P, P, P, P, LL, LL, I, P]),
+    }
+    for name, (restype, argtypes) in expect.items():
+        fn = _lib._fns[name]
+        assert fn.restype is restype, name
+        assert len(fn.argtypes) == len(argtypes) and all(a is b for a, b in zip(fn.argtypes, argtypes)), name
+
+
+def test_bf16_twins_share_their_base_signature():
+    from multimodal_gar_amd import _lib
+    assert len(_lib.BF16_TWINS) == 27
+    assert _lib.BF16_TWINS == {n[:-5] for n in _lib._fns if n.endswith("_bf16")}
+    for base in _lib.BF16_TWINS:
+        twin = _lib._fns[base + "_bf16"]
+        assert list(twin.argtypes) == list(_lib._fns[base].argtypes), base
+        assert twin.restype is _lib._fns[base].restype, base
+
+
+def test_header_parser_is_strict():
+    """A type the binding does not know must fail the import, not bind as something plausible."""
+    from multimodal_gar_amd import _lib
+    version = "#define MGAR_ABI_VERSION 7\n"
+    I, F, D, LL, P = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p
+    ok = version + """
+        /* a comment naming mgar_not_a_function(int) */
+        #define MGAR_SOMETHING 3
+        extern "C" {
+        int mgar_a(void);   // trailing mgar_comment(unsigned n);
+        long long mgar_b(int n, long long total,
+                         float r, double d,
+                         const float *x, int *const *idx, const unsigned char *arg, void *stream);
+        const char *mgar_c(int id);
+        }
+    """
+    assert _lib._parse_header(ok) == (7, {"mgar_a": (I, []), "mgar_b": (LL, [I, LL, F, D, P, P, P, P]),
+                                          "mgar_c": (ctypes.c_char_p, [I])})
+    for bad in ("int mgar_x(unsigned n);", "int mgar_x(size_t n);", "int mgar_x(struct mgar_box box);",
+                "int mgar_x(mgar_box box);", "int mgar_x(int (*callback)(int));", "unsigned mgar_x(int n);",
+                "char *mgar_x(int n);", "float *mgar_x(int n);", "int mgar_x(int);", "int mgar_x(int n); int mgar_x(int n);",
+                "struct mgar_box { int n; };"):
+        with pytest.raises(ImportError):
+            _lib._parse_header(version + bad)
+    with pytest.raises(ImportError):
+        _lib._parse_header("int mgar_x(int n);")        # no MGAR_ABI_VERSION
 
 
 def test_invalid_arguments_return_codes_not_exit():
