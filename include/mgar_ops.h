@@ -31,7 +31,7 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
-#define MGAR_ABI_VERSION 13     /* bumped on any signature change; mgar_abi_version() returns it */
+#define MGAR_ABI_VERSION 14     /* bumped on any signature change; mgar_abi_version() returns it */
 
 /* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
@@ -508,6 +508,16 @@ long long mgar_conv3d_k3_workspace_floats(int Cin, int Cout);
 int mgar_conv3d_k3_set_lds_pad(int bytes);   /* diagnostics: extra dynamic LDS per workgroup (occupancy experiments), default 0 */
 int mgar_conv3d_k3_fwd(const float *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, float *w_packed, float *y,
                        void *stream);
+/* The same units for bf16 payloads (the bf16 forward configurations), as a DIRECT convolution on the bf16 MFMA: x and y bf16
+ * NCDHW, w the fp32 (Cout, Cin, 3, 3, 3) master weight, rounded to bf16 (nearest even) when it is packed -- the stem's
+ * convention.  Products are exact in the fp32 accumulator; the result is rounded once on store.  Cin % 8 == 0 and even W, any
+ * Cout; anything else returns MGAR_EINVAL before any device call.  w_packed: caller-allocated scratch of
+ * mgar_conv3d_k3_bf16_workspace_bytes(Cin, Cout) bytes, 16-byte aligned (28 672 per 64 output x 8 input channels, rewritten on
+ * every call).  No atomics: sample n of the result does not depend on N.  Not a `_bf16` twin of mgar_conv3d_k3_fwd (other
+ * signature): called by name.  Forward only. */
+long long mgar_conv3d_k3_bf16_workspace_bytes(int Cin, int Cout);
+int mgar_conv3d_k3_bf16_fwd(const void *x, int N, int Cin, int D, int H, int W, const float *w, int Cout,
+                            void *w_packed, void *y, void *stream);
 
 /* ===================== third-party ops on the hot path ================================ */
 

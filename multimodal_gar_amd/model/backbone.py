@@ -127,12 +127,35 @@ class Unit3D(nn.Module):
         return y
 
     gemm_1x1 = os.environ.get("MGAR_I3D_GEMM_1X1", "1") != "0"        # 1x1x1 units on the device: library GEMMs (one per sample) instead of the library convolution
-    wino_kernel = os.environ.get("MGAR_I3D_OWN_CONV", "1") != "0"     # 3x3x3, stride 1 on the device: csrc/conv3d_wino.hip (Winograd F(2,3) along W on the fp32 MFMA)
+    wino_kernel = os.environ.get("MGAR_I3D_OWN_CONV", "1") != "0"     # 3x3x3, stride 1 on the device: csrc/conv3d_wino.hip (Winograd F(2,3) along W on the fp32 MFMA); bf16 payloads: csrc/conv3d_bf16.hip (direct, bf16 MFMA)
+
+    def _k3_conv_bf16(self, x):
+        """bf16 payloads (the bf16 forward configurations, autocast on or off): csrc/conv3d_bf16.hip, a direct convolution on the
+        bf16 MFMA, bf16 NCDHW in and out; the weight (bf16 as ForwardStep converts it, or fp32) goes in as fp32 and is rounded to
+        bf16 when the kernel packs it, as in _stem_conv.  Or None."""
+        c = self.conv3d
+        if not (self.wino_kernel and x.is_cuda and x.dim() == 5 and x.dtype == torch.bfloat16
+                and self._kernel_shape == (3, 3, 3) and self._stride == (1, 1, 1) and c.bias is None and c.groups == 1
+                and c.in_channels % 8 == 0 and x.shape[4] % 2 == 0 and x.is_contiguous()
+                and c.weight.dtype in (torch.bfloat16, torch.float32)
+                and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad))):
+            return None
+        from .. import _lib as L
+        n, cin, d, h, w = x.shape
+        y = torch.empty((n, c.out_channels, d, h, w), dtype=torch.bfloat16, device=x.device)
+        wp = torch.empty((L.raw("mgar_conv3d_k3_bf16_workspace_bytes", cin, c.out_channels),), dtype=torch.uint8, device=x.device)
+        wf = c.weight.detach().float().contiguous()
+        L.call("mgar_conv3d_k3_bf16_fwd", L.pptr(x, torch.bfloat16), n, cin, d, h, w, L.fptr(wf), c.out_channels, wp.data_ptr(),
+               L.pptr(y, torch.bfloat16), L.stream_of(x))
+        return y
 
     def _k3_conv(self, x):
         """The 3x3x3 / stride-1 units (Conv3d_2c_3x3, every Mixed block's Conv3d_0b_3x3) on csrc/conv3d_wino.hip: "same"
-        padding inside the kernel, NCDHW in and out, fp32, forward only; or None (the library convolution then)."""
+        padding inside the kernel, NCDHW in and out, fp32, forward only; bf16 inputs: _k3_conv_bf16; or None (the library
+        convolution then)."""
         c = self.conv3d
+        if x.dtype == torch.bfloat16:
+            return self._k3_conv_bf16(x)
         if not (self.wino_kernel and x.is_cuda and x.dim() == 5 and x.dtype == torch.float32 and not torch.is_autocast_enabled()
                 and self._kernel_shape == (3, 3, 3) and self._stride == (1, 1, 1) and c.bias is None and c.groups == 1
                 and c.in_channels % 2 == 0 and x.shape[4] % 2 == 0 and x.is_contiguous() and c.weight.dtype == torch.float32
@@ -155,7 +178,8 @@ class Unit3D(nn.Module):
         if k3 is not None:
             return k3
         if (self.gemm_1x1 and x.is_cuda and x.dim() == 5 and self._kernel_shape == (1, 1, 1) and self._stride == (1, 1, 1)
-                and x.is_contiguous() and self.conv3d.groups == 1 and not torch.is_autocast_enabled()
+                and x.is_contiguous() and self.conv3d.groups == 1
+                and (not torch.is_autocast_enabled() or x.dtype == torch.bfloat16)     # operands already bf16: nothing for autocast to cast (out= GEMMs are not re-cast)
                 and x.dtype == self.conv3d.weight.dtype
                 and not (torch.is_grad_enabled() and (x.requires_grad or self.conv3d.weight.requires_grad))):
             # a 1x1x1 convolution is the GEMM W (C_out, C_in) x (C_in, T*H*W) per sample, on the NCDHW tensor as it lies (MIOpen
