@@ -587,7 +587,10 @@ long long mgar_gatv2_bwd_workspace_floats(int n_nodes, int H, int C, int n_edges
  * relative coordinates, so first and second moments of those suffice): moments[10] doubles = E[r] (3), Cov(r) (6: xx, xy,
  * xz, yy, yz, zz), n; mean / invstd (C) feed _fwd and _bwd; running statistics get the usual momentum update.
  * bwd: dfeats (N, ld_f) is ACCUMULATED into (caller zero-fills; may be NULL), dgamma / dbeta (C) and dw_pos (C, 3) are
- * written; train_stats = 0 treats mean / invstd as constants (eval-mode BatchNorm). */
+ * written; train_stats = 0 treats mean / invstd as constants (eval-mode BatchNorm).
+ * Workspaces: _stats takes 9 doubles per workgroup of its moments pass, min(2048, max(1, ceil(M * nsample / 2048))) of
+ * them; _bwd takes 5 * C floats per 64 queries, ceil(M / 64) * C * 5.  Both size queries return MGAR_EINVAL for a
+ * negative argument. */
 long long mgar_voxel_roi_pool_stats_workspace_doubles(int M, int nsample);
 long long mgar_voxel_roi_pool_bwd_workspace_floats(int M, int C);
 int mgar_voxel_roi_pool_stats(int M, int nsample, int C, const float *xyz, const float *new_xyz, const int *idx,

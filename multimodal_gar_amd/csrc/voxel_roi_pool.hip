@@ -48,20 +48,24 @@ __global__ __launch_bounds__(VP_THREADS) void vrp_moments_kernel(long long total
                                                                  const float *__restrict__ new_xyz, const int *__restrict__ idx,
                                                                  double *__restrict__ partial) {
     __shared__ double scratch[VP_THREADS / 64];
-    float s[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // r is the fp32 difference the forward uses; its products and all sums are taken in double.  The finalize step forms
+    // Cov = E[r r^T] - E[r] E[r]^T, and a product rounded to fp32 (6e-8 relative) does not cancel there: with few columns or
+    // |E[r]| >> std(r) that rounding, times |w|^2, is comparable with var + eps (n = 1: var = 0 exactly, eps = 1e-5, and
+    // invstd came out 2.5e-4 off).  A product of two fp32 numbers is exact in double.
+    double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (long long e = (long long)blockIdx.x * VP_THREADS + threadIdx.x; e < total; e += (long long)gridDim.x * VP_THREADS) {
         const long long m = e / nsample;
         if (idx[m * nsample] < 0) continue;   // empty neighbourhood: r = 0
         const int j = idx[e];
-        const float rx = xyz[(size_t)j * 3 + 0] - new_xyz[m * 3 + 0];
-        const float ry = xyz[(size_t)j * 3 + 1] - new_xyz[m * 3 + 1];
-        const float rz = xyz[(size_t)j * 3 + 2] - new_xyz[m * 3 + 2];
+        const double rx = (double)(xyz[(size_t)j * 3 + 0] - new_xyz[m * 3 + 0]);
+        const double ry = (double)(xyz[(size_t)j * 3 + 1] - new_xyz[m * 3 + 1]);
+        const double rz = (double)(xyz[(size_t)j * 3 + 2] - new_xyz[m * 3 + 2]);
         s[0] += rx; s[1] += ry; s[2] += rz;
         s[3] += rx * rx; s[4] += rx * ry; s[5] += rx * rz; s[6] += ry * ry; s[7] += ry * rz; s[8] += rz * rz;
     }
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
-        const double t = block_sum_f64((double)s[k], scratch);
+        const double t = block_sum_f64(s[k], scratch);
         if (threadIdx.x == 0) partial[(size_t)blockIdx.x * 9 + k] = t;
     }
 }

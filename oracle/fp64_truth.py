@@ -14,7 +14,8 @@ so that a test can assert  err(HIP vs truth) <= 1.5 * err(oracle backend vs trut
 
 Compositions follow the reference modules: pointnet2_batch/pointnet2_modules.py:19-55 (SA, MSG) and :122-170 (FP),
 pointnet2_stack/pointnet2_modules.py:78-112 (stack SA) and :129-157 (stack FP), with QueryAndGroup as
-pointnet2_batch/pointnet2_utils.py:231-264 and pointnet2_stack/pointnet2_utils.py:112-159.
+pointnet2_batch/pointnet2_utils.py:231-264 and pointnet2_stack/pointnet2_utils.py:112-159; the Voxel-RoI pooling layer is
+pointnet2_stack/voxel_pool_modules.py:70-130.
 """
 import copy
 
@@ -129,3 +130,26 @@ def stack_fp(mod64, unknown, unknown_cnt, known, known_cnt, unknown_feats, known
     merged = spread if unknown_feats is None else torch.cat([spread, unknown_feats], 1)
     x = mod64.mlp(merged.permute(1, 0)[None, :, :, None])
     return x.squeeze(0).squeeze(-1).permute(1, 0)
+
+
+def voxel_sa_msg(mod64, xyz, xyz_cnt, new_xyz, new_cnt, new_coords, features, voxel2point_indices):
+    """NeighborVoxelSAModuleMSG.forward in float64.  xyz (N, 3) / new_xyz (M, 3) fp32-valued, new_coords (M, 4) [b, x, y, z],
+    features (N, C) float64 -> (M, sum C_out) float64.  The position branch runs through the module's own Conv2d +
+    BatchNorm2d on the (1, 3, M, nsample) relative coordinates: its statistics are measured, as in the reference."""
+    xyz32, new32 = _np32(xyz), _np32(new_xyz)
+    xyz64, new64 = torch.from_numpy(xyz32).double(), torch.from_numpy(new32).double()
+    zyx = np.ascontiguousarray(new_coords.detach().cpu().numpy().astype(np.int32)[:, [0, 3, 2, 1]])
+    table = np.ascontiguousarray(voxel2point_indices.detach().cpu().numpy().astype(np.int32))
+    outs = []
+    for k, grouper in enumerate(mod64.groupers):
+        feats_in = mod64.mlps_in[k](features.permute(1, 0).unsqueeze(0)).squeeze(0).permute(1, 0)     # (N, C)
+        raw = torch.from_numpy(O.voxel_query(grouper.max_range, grouper.radius, grouper.nsample, xyz32, new32, zyx,
+                                             table).astype(np.int64))
+        empty = raw[:, 0] == -1
+        rows = raw.clamp_min(0).masked_fill(empty[:, None], 0)                                        # (M, ns) global rows
+        keep = (~empty).double()[:, None, None]
+        g = feats_in[rows].permute(0, 2, 1) * keep                                                    # (M, C, ns)
+        rel = (xyz64[rows] - new64[:, None, :]).permute(0, 2, 1) * keep                               # (M, 3, ns)
+        x = torch.relu(g.permute(1, 0, 2)[None] + mod64.mlps_pos[k](rel.permute(1, 0, 2)[None]))      # (1, C, M, ns)
+        outs.append(mod64.mlps_out[k](x.max(dim=3).values).squeeze(0).permute(1, 0))
+    return torch.cat(outs, 1)

@@ -2,6 +2,7 @@
 by the GPU tests for value AND gradient parity.  They restate the published definitions
 independently of both the HIP kernels and the C oracle."""
 import math
+from types import SimpleNamespace
 
 import torch
 
@@ -75,3 +76,84 @@ def gatv2_ref(x, edge_index, lin_l, lin_r, att, bias, heads, out_ch, slope=0.2, 
     out = torch.stack(out)
     out = out.reshape(n, heads * out_ch) if concat else out.mean(1)
     return out + bias
+
+
+def voxel_roi_pool_ref(xyz, new_xyz, feats, idx_raw, w_pos, gamma, beta, eps, train, running_mean=None, running_var=None,
+                       momentum=0.1, dtype=torch.float64):
+    """One scale of the reference's NeighborVoxelSAModuleMSG between mlps_in and mlps_out (voxel_pool_modules.py:86-126)
+    as its op chain, in float64 with autograd: gather the voxel rows, zero the rows of empty neighbourhoods
+    (idx_raw[m, 0] == -1), relative coordinates r, p = w_pos . r, BatchNorm2d over ALL M * nsample columns (the biased
+    variance normalises, the unbiased one goes into the running update; empty columns count), add the features, ReLU,
+    max over nsample.  Every statistic is MEASURED on the (M, C, nsample) tensor; nothing here is a closed form.
+
+    xyz (N, 3), new_xyz (M, 3), idx_raw (M, nsample) integer; feats (N, C) or None (statistics only: the returned
+    pooled / pre / arg are None); w_pos (C, 3); gamma / beta (C) or None (no affine); train False normalises with
+    running_mean / running_var.  Tensors that require grad must already be float64.  dtype=torch.float32 evaluates the
+    same chain in fp32 (the yardstick for cancellation-limited sums, see test_voxel_roi_pool_gpu.py); everything that is
+    compared against is the float64 default.
+
+    Returns a namespace: pooled (C, M), pre (M, C, nsample) before the ReLU, arg (M, C) the FIRST slot that attains the
+    maximum, mean / var (C; var biased), moments (10) = E[r], Cov(r) (biased: xx, xy, xz, yy, yz, zz), n, r (M, nsample,
+    3), and running_mean / running_var after the momentum update (None where none was given).  n == 1 has no unbiased
+    variance (torch refuses to train on one value per channel); the running update then keeps the biased one, 0."""
+    f64 = lambda t: None if t is None else torch.as_tensor(t).to(dtype)   # noqa: E731
+    xyz, new_xyz, w_pos, gamma, beta = f64(xyz), f64(new_xyz), f64(w_pos), f64(gamma), f64(beta)
+    idx = torch.as_tensor(idx_raw).long()
+    n_query, nsample = idx.shape
+    empty = idx[:, 0] == -1
+    rows = idx.clamp_min(0).masked_fill(empty[:, None], 0)
+    keep = (~empty).to(dtype)
+    r = (xyz[rows] - new_xyz[:, None, :]) * keep[:, None, None]                                  # (M, ns, 3)
+    p = torch.einsum("ck,msk->mcs", w_pos, r)                                                    # (M, C, ns)
+    n = n_query * nsample
+    if train:
+        mean = p.mean(dim=(0, 2))
+        var = ((p - mean[None, :, None]) ** 2).mean(dim=(0, 2))
+    else:
+        mean, var = f64(running_mean), f64(running_var)
+    bn = (p - mean[None, :, None]) / torch.sqrt(var[None, :, None] + eps)
+    if gamma is not None:
+        bn = bn * gamma[None, :, None]
+    if beta is not None:
+        bn = bn + beta[None, :, None]
+    out = SimpleNamespace(pooled=None, pre=None, arg=None, mean=mean, var=var, r=r, running_mean=None, running_var=None)
+    flat = r.detach().reshape(-1, 3)
+    er = flat.mean(0)
+    cov = (flat - er).t() @ (flat - er) / max(n, 1)
+    out.moments = torch.stack([er[0], er[1], er[2], cov[0, 0], cov[0, 1], cov[0, 2], cov[1, 1], cov[1, 2], cov[2, 2],
+                               torch.tensor(float(n), dtype=dtype)])
+    if train and running_mean is not None:
+        out.running_mean = (1.0 - momentum) * f64(running_mean) + momentum * mean.detach()
+    if train and running_var is not None:
+        unbiased = var.detach() * (n / (n - 1.0)) if n > 1 else var.detach()
+        out.running_var = (1.0 - momentum) * f64(running_var) + momentum * unbiased
+    if feats is None:
+        return out
+    feats = torch.as_tensor(feats)
+    g = feats[rows].permute(0, 2, 1) * keep[:, None, None]                                        # (M, C, ns)
+    pre = g + bn
+    top = pre.detach().max(dim=2, keepdim=True).values
+    slots = torch.arange(nsample).expand_as(pre)
+    arg = torch.where(pre.detach() == top, slots, torch.full_like(slots, nsample)).min(dim=2).values
+    # max over nsample through the first arg-max slot: equal values (first-hit padding repeats a row) carry equal gradients
+    out.pooled = torch.relu(pre.gather(2, arg[:, :, None]).squeeze(2)).t()
+    out.pre, out.arg = pre, arg
+    return out
+
+
+def near_tie_mask(values, idx_raw, margin):
+    """(M, C) bool: entries whose best value over nsample is closer than margin * max |values| to the best value of a
+    DIFFERENT voxel row -- there an fp32 evaluation may legitimately pick another neighbour than float64 does.  values
+    (M, C, nsample), idx_raw (M, nsample).  A row repeated by first-hit padding carries an identical value in every
+    evaluation and is no tie: both sides take the first slot.  Empty neighbourhoods are one (zero) row: never masked."""
+    values = values.detach()
+    idx = torch.as_tensor(idx_raw).long()
+    if values.numel() == 0:
+        return torch.zeros(values.shape[:2], dtype=torch.bool)
+    empty = idx[:, 0] == -1
+    rows = idx.clamp_min(0).masked_fill(empty[:, None], 0)
+    best, slot = values.max(dim=2)
+    best_row = rows.gather(1, slot)                                                               # (M, C)
+    other = rows[:, None, :] != best_row[:, :, None]                                              # (M, C, ns)
+    rival = values.masked_fill(~other, -math.inf).max(dim=2).values
+    return (best - rival) < margin * values.abs().max()

@@ -72,7 +72,9 @@ class Case:
 def cases():
     from multimodal_gar_amd.pcdet.ops.pointnet2.pointnet2_batch import pointnet2_modules as MB
     from multimodal_gar_amd.pcdet.ops.pointnet2.pointnet2_stack import pointnet2_modules as MS
+    from multimodal_gar_amd.pcdet.ops.pointnet2.pointnet2_stack import voxel_pool_modules as MV
     from oracle import fp64_truth as T
+    import module_cases
     out = []
     g = torch.Generator().manual_seed(7)
     xyz = _scene(1, 2, 1024)
@@ -107,6 +109,11 @@ def cases():
     out.append(Case("fp_stack", lambda: MS.StackPointnetFPModule(mlp=[15, 20]),
                     [(sx, False), (cnt, False), (q, False), (qcnt, False), (sf, True), (kf2, True)],
                     lambda m, *a: m(*a), T.stack_fp))
+    # Voxel-RoI pooling: the fixture's sparse voxel grid and constructor arguments (tests/golden/module_cases.py); on the
+    # device this is the fused path with closed-form BatchNorm statistics (csrc/voxel_roi_pool.hip)
+    vcase = next(c for c in module_cases.CASES if c["name"] == "voxel_sa_msg")
+    out.append(Case("voxel_sa_msg", lambda: MV.NeighborVoxelSAModuleMSG(**vcase["kwargs"]()), module_cases._voxel_sa(vcase["seed"]),
+                    lambda m, *a: m(*a), T.voxel_sa_msg))
     return out
 
 
