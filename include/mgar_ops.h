@@ -539,7 +539,10 @@ int mgar_roi_align_bwd(const float *grad_out, int N, int C, int H, int W, const 
  *   out = Att V
  * q,k,v,out: (rows, D) row-major, D a multiple of 64; de: per scene a dense (n_s, n_s)
  * block stored at de + de_off[s].  att (same layout as de) is saved for the backward.
- * total_rows = scene_off[S] is passed by the host (it sizes the grid). */
+ * total_rows = scene_off[S] is passed by the host (it sizes the grid).
+ * The kernels keep MGAR_DAFM_MAX_N / 64 columns per lane.  scene_off is a device pointer, so
+ * these entries CANNOT check n_s: the caller must reject n_s > MGAR_DAFM_MAX_N before the call
+ * (the Python layer does in dafm_ops.scene_offsets); a larger scene gives a wrong result. */
 #define MGAR_DAFM_MAX_N 128
 int mgar_dafm_attn_fwd(int S, int total_rows, int D, const int *scene_off, const int *de_off, const float *q, const float *k,
                        const float *v, const float *de, float sigma, float scale, float *att, float *out,

@@ -25,13 +25,20 @@ if not os.path.exists(HEADER_PATH):
 _SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong}
 
 
+def _header_int(text, name):
+    """Value of `#define <name> <n>` in the text of include/mgar_ops.h (None if absent)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    m = re.search(r"^#define %s (\d+)\s*$" % re.escape(name), text, flags=re.M)
+    return int(m.group(1)) if m else None
+
+
 def _parse_header(text):
     """(MGAR_ABI_VERSION, {name: (restype, [argtypes])}) of every mgar_* declaration in the text of include/mgar_ops.h.
     Strict on purpose: int / float / double / long long, pointers (void *) and a `const char *` result are all the ABI
     uses; a declaration with anything else raises instead of binding as something plausible."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    version = re.search(r"^#define MGAR_ABI_VERSION (\d+)\s*$", text, flags=re.M)
-    if not version:
+    version = _header_int(text, "MGAR_ABI_VERSION")
+    if version is None:
         raise ImportError("mgar_ops.h: no `#define MGAR_ABI_VERSION <n>`")
     text = re.sub(r'^[ \t]*#[^\n]*|extern\s+"C"\s*\{|\}', " ", text, flags=re.M)
     protos = {}
@@ -48,11 +55,15 @@ def _parse_header(text):
         if restype is None or None in argtypes or name in protos:
             raise ImportError("mgar_ops.h: unsupported type or duplicate in `%s`" % decl)
         protos[name] = (restype, argtypes)
-    return int(version.group(1)), protos
+    return version, protos
 
 
 with open(HEADER_PATH) as _f:
-    ABI_VERSION, _protos = _parse_header(_f.read())
+    _header = _f.read()
+ABI_VERSION, _protos = _parse_header(_header)
+DAFM_MAX_N = _header_int(_header, "MGAR_DAFM_MAX_N")   # actors per scene the DAFM kernels hold in registers
+if DAFM_MAX_N is None:
+    raise ImportError("mgar_ops.h: no `#define MGAR_DAFM_MAX_N <n>`")
 BF16_TWINS = frozenset(n[:-5] for n in _protos if n.endswith("_bf16"))
 
 _cdll = ctypes.CDLL(LIB_PATH)

@@ -33,6 +33,17 @@ __device__ __forceinline__ int scene_of_row(int row, int S, const int *__restric
     return lo;
 }
 
+// Column j of a row held lanes-along-j (r[t] of lane l is column l + t * kWave), wave-uniform.  The loops that call this
+// run lanes-along-d with only D / 4 lanes active when D < 256 (and on a partial last trip), so the register must be
+// picked on the SCALAR side: a per-lane select (j < kWave ? r[0] : r[1]) would be written for the active lanes only, and
+// v_readlane of an inactive lane would return a stale value -- wrong results for j >= D / 4.  r[t] itself is complete:
+// it was computed with all lanes active.
+__device__ __forceinline__ float bcast_col(const float (&r)[DAFM_JPL], int j) {
+    const int lo = __builtin_amdgcn_readlane(__builtin_bit_cast(int, r[0]), j & 63);
+    const int hi = __builtin_amdgcn_readlane(__builtin_bit_cast(int, r[1]), j & 63);
+    return __builtin_bit_cast(float, j < kWave ? lo : hi);
+}
+
 // grid: ceil(total_rows / 4) workgroups of 4 waves
 __global__ __launch_bounds__(256) void dafm_fwd_kernel(int S, int total_rows, int D, const int *__restrict__ scene_off,
                                                        const int *__restrict__ de_off, const float *__restrict__ q,
@@ -101,7 +112,7 @@ __global__ __launch_bounds__(256) void dafm_fwd_kernel(int S, int total_rows, in
     for (int d0 = lane * 4; d0 < D; d0 += 256) {
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int j = 0; j < n; ++j) {
-            const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, j < kWave ? p[0] : p[1]), j & 63));
+            const float a = bcast_col(p, j);
             const float4 vv = *reinterpret_cast<const float4 *>(v + (size_t)(r0 + j) * D + d0);
             acc.x += a * vv.x; acc.y += a * vv.y; acc.z += a * vv.z; acc.w += a * vv.w;
         }
@@ -170,7 +181,7 @@ __global__ __launch_bounds__(256) void dafm_bwd_rows_kernel(int S, int total_row
     for (int d0 = lane * 4; d0 < D; d0 += 256) {
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int j = 0; j < n; ++j) {
-            const float gj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, j < kWave ? g[0] : g[1]), j & 63));
+            const float gj = bcast_col(g, j);
             const float4 kk = *reinterpret_cast<const float4 *>(k + (size_t)(r0 + j) * D + d0);
             acc.x += gj * kk.x; acc.y += gj * kk.y; acc.z += gj * kk.z; acc.w += gj * kk.w;
         }

@@ -19,6 +19,7 @@ class _DafmAttention(Function):
                L.fptr(v), L.fptr(de_flat), float(sigma), float(scale), L.fptr(att), L.fptr(out), L.stream_of(q))
         ctx.save_for_backward(q, k, v, de_flat, scene_off, de_off, att)
         ctx.cfg = (float(sigma), float(scale))
+        ctx.mark_non_differentiable(att)      # backward has no gradient path through att
         return out, att
 
     @staticmethod
@@ -41,11 +42,17 @@ _OFFSET_CACHE = {}
 
 def scene_offsets(counts, device):
     """counts: python list of actors per scene -> (scene_off (S+1,), de_off (S,)) int32 on device.
-    Cached per (counts, device): no host->device copy in the steady state (and none under graph capture)."""
+    Cached per (counts, device): no host->device copy in the steady state (and none under graph capture).
+    The kernels hold a scene's columns in registers, MGAR_DAFM_MAX_N (include/mgar_ops.h) at the most; the C entry sees
+    only device pointers, so the limit is enforced here, where the counts are still a host list."""
     key = (tuple(int(c) for c in counts), str(device))
     hit = _OFFSET_CACHE.get(key)
     if hit is not None:
         return hit
+    for n in counts:
+        if not 0 <= int(n) <= L.DAFM_MAX_N:
+            raise ValueError("dafm: a scene of %d actors is outside 0..%d (MGAR_DAFM_MAX_N), the capacity of the "
+                             "attention kernels" % (int(n), L.DAFM_MAX_N))
     so, do, r, m = [0], [], 0, 0
     for n in counts:
         do.append(m)

@@ -38,6 +38,7 @@ class _GatAggregate(Function):
             by_source = csr_by_source(rowptr, col)
         ctx.save_for_backward(xl, xr, att, rowptr, col, alpha, edge_scale if edge_scale is not None else torch.empty(0), *by_source)
         ctx.cfg = (heads, float(slope), edge_scale is not None)
+        ctx.mark_non_differentiable(alpha)    # backward has no gradient path through alpha
         return out, alpha
 
     @staticmethod

@@ -8,12 +8,18 @@ import torch
 
 
 def roi_align_ref(inp, rois, out_size, scale, sampling_ratio=-1, aligned=False):
+    """RoIAlign in float64 with autograd.  out_size: int or (ph, pw).  Every bin is summed on its own -- one gather of
+    its bilinear taps from the (C, H*W) plane of its image, weights applied, taps added up -- and the bins are stacked at
+    the end, so autograd never copies a (C, ph, pw) block per tap.  Same arithmetic per tap as the published definition;
+    only the order in which one bin's taps are added differs from a running sum (reassociation, a few ulp of float64)."""
     inp = inp.double()
     K = rois.shape[0]
-    _, C, H, W = inp.shape
-    ph = pw = out_size
-    out = []
+    N, C, H, W = inp.shape
+    ph, pw = (out_size, out_size) if isinstance(out_size, int) else out_size
+    planes = [inp[b].reshape(C, H * W) for b in range(N)]       # one select per image, shared by all of its RoIs
     off = 0.5 if aligned else 0.0
+    zero = torch.zeros(C, dtype=torch.float64, device=inp.device)
+    bins = []
     for k in range(K):
         b = int(rois[k, 0].item())
         x1, y1, x2, y2 = [float(v) * scale - off for v in rois[k, 1:]]
@@ -23,9 +29,10 @@ def roi_align_ref(inp, rois, out_size, scale, sampling_ratio=-1, aligned=False):
         bw, bh = rw / pw, rh / ph
         gh = sampling_ratio if sampling_ratio > 0 else math.ceil(rh / ph)
         gw = sampling_ratio if sampling_ratio > 0 else math.ceil(rw / pw)
-        acc = torch.zeros((C, ph, pw), dtype=torch.float64, device=inp.device)
+        count = max(gh * gw, 1)
         for p_h in range(ph):
             for p_w in range(pw):
+                idx, wgt = [], []
                 for iy in range(gh):
                     y = y1 + p_h * bh + (iy + 0.5) * bh / gh
                     for ix in range(gw):
@@ -44,10 +51,14 @@ def roi_align_ref(inp, rois, out_size, scale, sampling_ratio=-1, aligned=False):
                             xh = xl + 1
                         ly, lx = yy - yl, xx - xl
                         hy, hx = 1 - ly, 1 - lx
-                        acc[:, p_h, p_w] = acc[:, p_h, p_w] + hy * hx * inp[b, :, yl, xl] + hy * lx * inp[b, :, yl, xh] \
-                            + ly * hx * inp[b, :, yh, xl] + ly * lx * inp[b, :, yh, xh]
-        out.append(acc / max(gh * gw, 1))
-    return torch.stack(out)
+                        idx += [yl * W + xl, yl * W + xh, yh * W + xl, yh * W + xh]
+                        wgt += [hy * hx, hy * lx, ly * hx, ly * lx]
+                if not idx:
+                    bins.append(zero)
+                    continue
+                taps = planes[b][:, torch.tensor(idx, device=inp.device)] * torch.tensor(wgt, dtype=torch.float64, device=inp.device)
+                bins.append(taps.sum(1) / count)
+    return torch.stack(bins).reshape(K, ph, pw, C).permute(0, 3, 1, 2) if K else inp.new_zeros((0, C, ph, pw))
 
 
 def dafm_ref(q, k, v, de, sigma, scale):
@@ -56,26 +67,41 @@ def dafm_ref(q, k, v, de, sigma, scale):
     return att @ v, att
 
 
-def gatv2_ref(x, edge_index, lin_l, lin_r, att, bias, heads, out_ch, slope=0.2, concat=False, edge_scale=None):
-    """Dense-loop GATv2 with self loops re-added; edge_scale: dict {(j, i): (H,) tensor} or None."""
+def gatv2_ref(x, edge_index, lin_l, lin_r, att, bias, heads, out_ch, slope=0.2, concat=False, edge_scale=None,
+              add_self_loops=True, share_weights=False, return_alpha=False):
+    """Dense-loop GATv2 as PyG's GATv2Conv computes it.  add_self_loops: input self loops are dropped and one loop per
+    node is appended (otherwise the list is used as it is; a target without incoming edge then aggregates nothing and its
+    row is the bias).  Duplicate edges stay duplicates: each takes part in the softmax.  share_weights: x_r = x_l = lin_l(x).
+    bias may be None.  edge_scale: dict {(j, i): (H,) tensor} or None (it cannot tell duplicates apart: use it on graphs
+    without them).  return_alpha: also the (E', H) attention in CSR order -- grouped by target, ascending; within a
+    target in the order of the list (kept input edges first, the appended self loop last) -- before edge_scale."""
     n = x.shape[0]
     xl = lin_l(x).view(n, heads, out_ch)
-    xr = lin_r(x).view(n, heads, out_ch)
+    xr = xl if share_weights else lin_r(x).view(n, heads, out_ch)
     src, dst = edge_index[0].tolist(), edge_index[1].tolist()
-    pairs = [(j, i) for j, i in zip(src, dst) if j != i] + [(i, i) for i in range(n)]
-    out = []
+    if add_self_loops:
+        pairs = [(j, i) for j, i in zip(src, dst) if j != i] + [(i, i) for i in range(n)]
+    else:
+        pairs = list(zip(src, dst))
+    incoming = [[] for _ in range(n)]
+    for j, i in pairs:
+        incoming[i].append(j)
+    out, alphas = [], []
     a = att.view(heads, out_ch)
     for i in range(n):
-        js = [j for j, t in pairs if t == i]
+        js = incoming[i]
         z = torch.nn.functional.leaky_relu(xl[js] + xr[i][None], slope)      # (deg, H, C)
         e = (z * a[None]).sum(-1)                                           # (deg, H)
         al = torch.softmax(e, dim=0)
-        if edge_scale is not None:
+        alphas.append(al)
+        if edge_scale is not None and js:
             al = al * torch.stack([edge_scale[(j, i)] for j in js])
         out.append((al[:, :, None] * xl[js]).sum(0))
     out = torch.stack(out)
     out = out.reshape(n, heads * out_ch) if concat else out.mean(1)
-    return out + bias
+    if bias is not None:
+        out = out + bias
+    return (out, torch.cat(alphas)) if return_alpha else out
 
 
 def voxel_roi_pool_ref(xyz, new_xyz, feats, idx_raw, w_pos, gamma, beta, eps, train, running_mean=None, running_var=None,
