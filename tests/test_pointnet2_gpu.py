@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import torch_refs as R
+
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -462,8 +464,7 @@ def test_query_group_batch_backward_is_reproducible_and_exact(ops, n, npoint, ns
     k = np.stack([np.bincount(idx[b], minlength=n) for b in range(2)])[:, None, :]          # contributions per cell
     assert k.max() > 8
     row_max = np.abs(gf).max(axis=2, keepdims=True)
-    bound = np.spacing(np.abs(want).astype(np.float32)).astype(np.float64) + k * row_max * cols * 2.0 ** -61 \
-        + k * row_max * 2.0 ** -50                                                            # + the float64 reference's own
+    bound = R.qg_fixed_point_scatter_bound(want, k, row_max, cols)                             # shared with test_query_group_gpu.py
     err = np.abs(got.double().cpu().numpy() - want)
     assert (err <= bound).all(), "worst cell: err %g, bound %g" % (err.max(), bound[err > bound].min())
 

@@ -4,6 +4,7 @@ independently of both the HIP kernels and the C oracle."""
 import math
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 
@@ -183,3 +184,171 @@ def near_tie_mask(values, idx_raw, margin):
     other = rows[:, None, :] != best_row[:, :, None]                                              # (M, C, ns)
     rival = values.masked_fill(~other, -math.inf).max(dim=2).values
     return (best - rival) < margin * values.abs().max()
+
+
+# ---------------------------------------------------------------------------------------------- query and group
+# Float64 references of csrc/query_group.hip, and the rounding-count bounds its device test asserts
+# (tests/test_query_group_gpu.py; tests/test_query_group_cpu.py proves them satisfiable).  U32 = fp32 unit roundoff.
+U32 = 2.0 ** -24
+TINY32 = 2.0 ** -149
+
+
+def query_group_batch_ref(xyz, new_xyz, feats_or_zf, idx, wx=None):
+    """QueryAndGroup after the ball query, dense batches, in float64 from the fp32 operands.  xyz (b, n, 3), new_xyz
+    (b, m, 3), feats_or_zf (b, c, n) or None (c = 0), idx (b, m, ns) -> rel (b, 3, m, ns), y (b, c, m, ns) = the gathered
+    rows, plus wx (c, 3) . rel when wx is given ("project, then group").  Autograd flows through feats_or_zf and wx
+    (hand them in as float64 leaves)."""
+    xyz, new_xyz = torch.as_tensor(xyz).double(), torch.as_tensor(new_xyz).double()
+    idx = torch.as_tensor(idx).long()
+    b, m, ns = idx.shape
+    flat = idx.reshape(b, m * ns)
+    near = torch.gather(xyz, 1, flat[:, :, None].expand(-1, -1, 3)).view(b, m, ns, 3)
+    rel = (near - new_xyz[:, :, None, :]).permute(0, 3, 1, 2)
+    if feats_or_zf is None:
+        y = rel.new_zeros((b, 0, m, ns))
+    else:
+        f = torch.as_tensor(feats_or_zf).double()
+        y = torch.gather(f, 2, flat[:, None, :].expand(-1, f.shape[1], -1)).view(b, f.shape[1], m, ns)
+    if wx is not None:
+        y = y + torch.einsum("ck,bkms->bcms", torch.as_tensor(wx).double(), rel)
+    return rel, y
+
+
+def stack_source_rows(xyz_cnt, new_cnt, idx_raw):
+    """(M, ns) int64: the global source row of every column of the raw stacked ball-query result, -1 for every slot of
+    an empty ball (idx_raw[row][0] == -1; its other slots hold arbitrary values and are ignored)."""
+    xyz_cnt, new_cnt = np.asarray(xyz_cnt, np.int64), np.asarray(new_cnt, np.int64)
+    idx = np.asarray(idx_raw, np.int64)
+    start = np.concatenate([[0], np.cumsum(xyz_cnt)[:-1]])
+    rows = idx + np.repeat(start, new_cnt)[:, None]
+    rows[idx[:, 0] == -1] = -1
+    return rows
+
+
+def query_group_stack_ref(xyz, xyz_cnt, new_xyz, new_cnt, feats_or_zf, idx_raw, wx=None):
+    """The same for stacked batches in the channel-major layout: xyz (N, 3), new_xyz (M, 3), feats_or_zf (N, C) (any
+    row stride) or None, idx_raw (M, ns) sample-local with the raw ball-query convention -> rel (3, M * ns), y
+    (C, M * ns).  The columns of an empty ball are zero in rel and y and carry nothing backward."""
+    xyz, new_xyz = torch.as_tensor(xyz).double(), torch.as_tensor(new_xyz).double()
+    rows = torch.from_numpy(stack_source_rows(xyz_cnt, new_cnt, idx_raw))
+    m, ns = rows.shape
+    live = rows[:, 0] >= 0
+    keep = live.double()[:, None, None]
+    src = torch.where(live[:, None], rows, torch.zeros_like(rows))
+    zeros3 = xyz.new_zeros((m, ns, 3))
+    rel = ((xyz[src] if xyz.shape[0] else zeros3) - new_xyz[:, None, :]) * keep
+    rel = rel.permute(2, 0, 1).reshape(3, m * ns)
+    if feats_or_zf is None:
+        y = rel.new_zeros((0, m * ns))
+    else:
+        f = torch.as_tensor(feats_or_zf).double()
+        g = f[src] if f.shape[0] else f.new_zeros((m, ns, f.shape[1]))
+        y = (g * keep).permute(2, 0, 1).reshape(f.shape[1], m * ns)
+    if wx is not None:
+        y = y + torch.as_tensor(wx).double() @ rel
+    return rel, y
+
+
+def qg_tile_stats_ref(y, chunk=128):
+    """y (C, T) with T % chunk == 0 -> float64 (tile_mean (C, T / chunk), tile_m2 (C, T / chunk), mean (C), var (C)):
+    per channel and tile of `chunk` consecutive columns the mean and the sum of squared deviations from it, and the
+    BatchNorm mean / biased variance the tiles finalise to through Chan's merge
+    (M2 = sum_t M2_t + chunk * sum_t (mean_t - mean)^2)."""
+    y = torch.as_tensor(y).detach().double()
+    c, t = y.shape
+    assert t % chunk == 0
+    tiles = y.view(c, t // chunk, chunk)
+    tile_mean = tiles.mean(2)
+    tile_m2 = ((tiles - tile_mean[:, :, None]) ** 2).sum(2)
+    mean = tile_mean.mean(1)
+    var = (tile_m2.sum(1) + chunk * ((tile_mean - mean[:, None]) ** 2).sum(1)) / max(t, 1)
+    return tile_mean, tile_m2, mean, var
+
+
+def qg_scatter_batch_ref(g, idx, n):
+    """Backward of the batch gather: g (b, c, cols), idx (b, cols) -> float64 numpy (want (b, c, n), k (b, 1, n) the
+    number of contributions of every cell, sabs (b, c, n) = sum |g| over them), by np.add.at."""
+    g, idx = np.asarray(g, np.float64), np.asarray(idx, np.int64)
+    b, c, _ = g.shape
+    want, sabs = np.zeros((b, c, n)), np.zeros((b, c, n))
+    for bi in range(b):
+        for ci in range(c):
+            np.add.at(want[bi, ci], idx[bi], g[bi, ci])
+            np.add.at(sabs[bi, ci], idx[bi], np.abs(g[bi, ci]))
+    k = np.stack([np.bincount(idx[bi], minlength=n) for bi in range(b)])[:, None, :].astype(np.float64)
+    return want, k, sabs
+
+
+def qg_scatter_stack_ref(g, rows, n):
+    """Backward of the stack gather: g (C, M * ns), rows = stack_source_rows(...) -> float64 numpy (want (n, C),
+    k (n, 1), sabs (n, C)); the columns of empty balls (row -1) contribute nothing."""
+    g, rows = np.asarray(g, np.float64), np.asarray(rows, np.int64).reshape(-1)
+    live = rows >= 0
+    want, sabs = np.zeros((n, g.shape[0])), np.zeros((n, g.shape[0]))
+    np.add.at(want, rows[live], g[:, live].T)
+    np.add.at(sabs, rows[live], np.abs(g[:, live].T))
+    k = np.bincount(rows[live], minlength=n)[:, None].astype(np.float64)
+    return want, k, sabs
+
+
+def qg_proj_fwd_bound(gathered, wx, rel):
+    """Elementwise bound of the fp32 "project, then group" forward against float64: 6 u (|zf| + sum_i |wx_i| |rel_i|)
+    + 2^-149.  One rounding in rel, one per product, two additions inside wx . rel and one onto zf: at most five on
+    any term, (1 + u)^5 - 1 < 6 u.  Contracting a product and an addition into an FMA only removes roundings.
+    gathered: |zf| at the columns, (b, c, m, ns) / (C, T); rel (b, 3, m, ns) / (3, T); wx (c, 3)."""
+    gathered, rel, wx = (torch.as_tensor(t).detach().double().abs() for t in (gathered, rel, wx))
+    mix = torch.einsum("ck,bkms->bcms", wx, rel) if rel.dim() == 4 else wx @ rel
+    return 6.0 * U32 * (gathered + mix) + TINY32
+
+
+def qg_fixed_point_scatter_bound(want, k, row_max, cols):
+    """Bound of qg_batch_bwd_lds_kernel (order-free 64-bit fixed point): every cell is the float64 scatter-add within one
+    fp32 rounding, plus k contributions each rounded by at most max|g of the row| * cols * 2^-61, plus the float64
+    reference's own k * max|g| * 2^-50.  numpy arrays that broadcast to want."""
+    return np.spacing(np.abs(want).astype(np.float32)).astype(np.float64) + k * row_max * cols * 2.0 ** -61 \
+        + k * row_max * 2.0 ** -50
+
+
+def qg_atomic_scatter_bound(want, k, sabs):
+    """Bound of a float-atomic scatter in any order: the first contribution lands exactly on the zeroed cell and each of
+    the other k - 1 additions rounds a partial sum no larger than sum |g|: (k - 1) u sum|g| + spacing(fp32(want)).
+    Cells nobody references (k = 0) get 0 here on purpose: they are asserted to be exactly 0."""
+    return np.where(k > 0, np.maximum(k - 1.0, 0.0) * U32 * sabs + np.spacing(np.abs(want).astype(np.float32)).astype(np.float64), 0.0)
+
+
+def qg_tile_stats_bounds(y, chunk=128):
+    """Bounds of the (mean, M2) partials qg_stack_fwd_kernel leaves per channel and 128-column tile, against
+    qg_tile_stats_ref of the SAME fp32 y, from the kernel's summation shape:
+      mean: eight sequential 16-term sums (15 roundings), a sequential sum of the eight (7 more), times 2^-7 (exact):
+            |d mean| <= g(22) * mean|v|,  g(j) = j u / (1 - j u);
+      M2:   two-pass about the computed mean: v - mean (1 rounding, squared: 2), the product (1), the same 15 + 7
+            additions: sum (v - mean_hat)^2 (1 + t), |t| <= g(25), and sum (v - mean_hat)^2 = M2 + chunk * d mean^2:
+            |d M2| <= g(25) * M2 + (1 + g(25)) * chunk * (d mean bound)^2.
+    An all-zero tile gives (0, 0) exactly; 2^-149 covers an underflow of the scaling by 2^-7.
+    Returns float64 (mean_bound, m2_bound), both (C, T / chunk)."""
+    y = torch.as_tensor(y).detach().double()
+    c, t = y.shape
+    tiles = y.view(c, t // chunk, chunk)
+    gamma = lambda j: j * U32 / (1.0 - j * U32)   # noqa: E731
+    _, m2, _, _ = qg_tile_stats_ref(y, chunk)
+    zero = (tiles == 0).all(2)
+    dmean = gamma(22) * tiles.abs().mean(2) + TINY32
+    dm2 = gamma(25) * m2 + (1.0 + gamma(25)) * chunk * dmean ** 2
+    return dmean.masked_fill(zero, 0.0), dm2.masked_fill(zero, 0.0)
+
+
+def qg_final_stats_bounds(y, eps, chunk=128):
+    """Bounds of mean / invstd that mgar_bn_stats_from_partials finalises from those partials (Chan's merge in double, one
+    fp32 rounding each at the end) against float64 of the same y.  With d = the largest tile-mean bound of the channel:
+      |d mean| <= average tile-mean bound + u |mean|;
+      |d var|  <= average(M2 bound) / chunk + average(4 d |mean_t - mean| + 4 d^2)     (both means move by <= d);
+      |d invstd| <= |d var| / 2 * (var + eps - |d var|)^-3/2 + u * invstd              ((v + eps)^-1/2 is convex).
+    Returns float64 (mean_bound (C), invstd_bound (C))."""
+    tile_mean, _, mean, var = qg_tile_stats_ref(y, chunk)
+    dmean_t, dm2_t = qg_tile_stats_bounds(y, chunk)
+    d = dmean_t.max(1).values
+    dvar = dm2_t.mean(1) / chunk + (4.0 * d[:, None] * (tile_mean - mean[:, None]).abs() + 4.0 * d[:, None] ** 2).mean(1)
+    low = var + eps - dvar
+    assert (low > 0).all()
+    invstd = (var + eps) ** -0.5
+    return dmean_t.mean(1) + U32 * mean.abs() + TINY32, 0.5 * dvar * low ** -1.5 + U32 * invstd
