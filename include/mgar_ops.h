@@ -31,7 +31,7 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
-#define MGAR_ABI_VERSION 14     /* bumped on any signature change; mgar_abi_version() returns it */
+#define MGAR_ABI_VERSION 15     /* bumped on any signature change; mgar_abi_version() returns it */
 
 /* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
@@ -471,6 +471,34 @@ int mgar_pointwise_conv_dw_bnbwd(const float *x, const float *dy, const float *w
 int mgar_pointwise_conv_fwd_stats(const float *x, int B, int Cin, int P, const float *w, int w_row_stride, int w_col_stride,
                                   int Cout, const float *in_mean, const float *in_invstd, const float *in_gamma,
                                   const float *in_beta, int in_relu, float *y, float *out_stats, void *stream);
+
+/* Backward of [conv 1x1 -> BatchNorm -> ReLU -> max over nsample] (the last layer of a shared MLP) without writing the
+ * max-pool layer's dense input gradient.  That gradient is a closed form of data already in memory,
+ *   dx4[b,c,m,s] = k_c * ((s == arg[b,c,m] ? dmask[b,c,m] : 0) - coef[2c] - (x4[b,c,m,s] - mean_c) * invstd_c * coef[2c+1]),
+ *   k_c = gamma_c * invstd_c,   x4 (B, C, M, nsample) = the max-pool layer's PRE-BatchNorm input,
+ * so its two consumers form it in their operand prologues (in the operation order of mgar_bn_act_maxpool_bwd: the same
+ * values enter the same MFMA chains) and read x4 where they would read dx4.
+ * mgar_bn_act_maxpool_bwd_reduce: the reduction half of mgar_bn_act_maxpool_bwd[_strided] alone -> dgamma, dbeta (C),
+ *   coef (2 C) = {mean dz, mean dz xhat} and dmask (B, C, M) contiguous = dpool, zeroed where relu != 0 and pooled <= 0.
+ *   dpool element (b, c, m) at dpool[b*sb + c*sc + m*sm]; sc < 0 = contiguous.  workspace: mgar_bn_workspace_floats(B, C,
+ *   M * nsample) floats.
+ * mgar_pointwise_conv_fwd_maxgrad: y (B, Cout, M * nsample) = W dx4 with w[o*w_row_stride + i*w_col_stride] (the data
+ *   gradient of the conv: its weight read transposed).
+ * mgar_pointwise_conv_dw_maxgrad: dw (Cout, Cin) = sum dx4[b,o,p] act(x)[b,i,p], x and its activation as in
+ *   mgar_pointwise_conv_dw_act; workspace: mgar_pointwise_dw_workspace_floats(B, Cin, Cout, M * nsample) floats.
+ * Both need nsample % 4 == 0 and at most 64 channels on either side (MGAR_EUNSUPPORTED otherwise).  fp32. */
+int mgar_bn_act_maxpool_bwd_reduce(const float *dpool, long long sb, long long sc, long long sm, const float *pooled,
+                                   const unsigned char *arg, const float *x, const float *xarg, int B, int C, int M,
+                                   int nsample, const float *mean, const float *invstd, int relu, float *workspace,
+                                   float *dgamma, float *dbeta, float *coef, float *dmask, void *stream);
+int mgar_pointwise_conv_fwd_maxgrad(const float *x4, int B, int Cin, int M, int nsample, const float *w, int w_row_stride,
+                                    int w_col_stride, int Cout, const float *mean, const float *invstd, const float *gamma,
+                                    const float *coef, const unsigned char *arg, const float *dmask, float *y, void *stream);
+int mgar_pointwise_conv_dw_maxgrad(const float *x, const float *x4, int B, int Cin, int Cout, int M, int nsample,
+                                   const float *in_mean, const float *in_invstd, const float *in_gamma,
+                                   const float *in_beta, int in_relu, const float *mean, const float *invstd,
+                                   const float *gamma, const float *coef, const unsigned char *arg, const float *dmask,
+                                   float *workspace, float *dw, void *stream);
 
 /* MaxPool3dSamePadding.forward of the reference's I3D (model/backbone.py:99-131): zero "same"
  * padding + max pooling without materialising the padded tensor.  x (NC, T, H, W) -> y (NC, ceil(T/st),

@@ -218,6 +218,86 @@ class _BnActConv(Function):
         return dx, dgamma, dbeta, None, None, None, dw, None, None
 
 
+class _BnActConvBnMaxPool(Function):
+    """pooled (B, Ck, M) = max_s relu2?(bn2(W . relu?(bn(x))))[b, :, m, s] for x (B, C, M * ns): the last two layers of a shared
+    MLP, [BN -> ReLU -> Conv 1x1] and [BN -> ReLU -> max over ns], as ONE autograd node.  The forward issues the launches of
+    _BnActConv followed by _BnActMaxPool.  The backward never writes the max-pool layer's input gradient (the widest tensor
+    of the module): after the reduction half of the max-pool backward, the conv's dX and dW kernels form it in their operand
+    prologues from the saved pre-BN tensor (csrc/pointwise_fwd.hip GRAD mode, csrc/pointwise_dw.hip GRAD instances) -- one
+    read and one write of that tensor less, bit for bit the same products."""
+
+    @staticmethod
+    def forward(ctx, x3, gamma, beta, mean, invstd, relu, w, gamma2, beta2, bn2, relu2, m, ns, rowmajor_grad=False):
+        b, c, p = x3.shape
+        ctx.rowmajor = bool(rowmajor_grad) and c <= ROWMAJOR_GRAD_MAX_CHANNELS
+        ck = w.shape[0]
+        w = w.contiguous()
+        st = L.stream_of(x3)
+        x4 = torch.empty((b, ck, m, ns), dtype=torch.float32, device=x3.device)
+        out_stats = stats_partial_buffer(x3, ck, b * p) if ck <= FUSED_STATS_MAX_CHANNELS and p % STATS_TILE == 0 else None
+        if out_stats is not None:
+            L.call("mgar_pointwise_conv_fwd_stats", L.fptr(x3), b, c, p, L.fptr(w), c, 1, ck, L.fptr(mean), L.fptr(invstd),
+                   L.fptr(gamma), L.fptr(beta), int(relu), L.fptr(x4), L.fptr(out_stats), st)
+        else:
+            L.call("mgar_pointwise_conv_fwd", L.fptr(x3), b, c, p, L.fptr(w), c, 1, ck, L.fptr(mean), L.fptr(invstd),
+                   L.fptr(gamma), L.fptr(beta), int(relu), L.fptr(x4), st)
+        mean2, invstd2 = _train_stats(x4.view(b, ck, p), bn2, out_stats)
+        out = torch.empty((b, ck, m), dtype=torch.float32, device=x3.device)
+        arg = torch.empty((b, ck, m), dtype=torch.uint8, device=x3.device)
+        xarg = torch.empty((b, ck, m), dtype=torch.float32, device=x3.device) if any(ctx.needs_input_grad) else None
+        L.call("mgar_bn_act_maxpool_fwd", L.fptr(x4), b, ck, m, ns, L.fptr(mean2), L.fptr(invstd2), L.fptr(gamma2), L.fptr(beta2),
+               int(relu2), L.fptr(out), _u8ptr(arg), L.fptr(xarg) if xarg is not None else None, st)
+        ctx.save_for_backward(x3, gamma, beta, mean, invstd, w, x4, gamma2, mean2, invstd2, out, arg, xarg)
+        ctx.relu, ctx.relu2 = bool(relu), bool(relu2)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dpool):
+        x3, gamma, beta, mean, invstd, w, x4, gamma2, mean2, invstd2, out, arg, xarg = ctx.saved_tensors
+        b, c, p = x3.shape
+        _, ck, m, ns = x4.shape
+        st = L.stream_of(x3)
+        dev = x3.device
+        # 1. reduction half of the max-pool layer's BatchNorm backward: coef2 = {mean dz, mean dz xhat}, and the masked pooled
+        #    gradient as a contiguous (B, Ck, M) array whatever the layout dpool came in
+        dgamma2, dbeta2 = torch.empty_like(gamma2), torch.empty_like(gamma2)
+        coef2 = torch.empty((2 * ck,), dtype=torch.float32, device=dev)
+        dmask = torch.empty((b, ck, m), dtype=torch.float32, device=dev)
+        ws2 = _workspace(x4, b, ck, p)
+        if dpool.dtype == torch.float32 and dpool.dim() == 3 and not dpool.is_contiguous() \
+                and (b == 1 or dpool.stride(0) >= 0) and min(dpool.stride(1), dpool.stride(2)) >= 1:
+            # a channel slice of the concatenated scales, or the transposed view of (M, C_total) rows: read in place
+            dp, strides = dpool, (dpool.stride(0) if b > 1 else 0, dpool.stride(1), dpool.stride(2))
+        else:
+            dp, strides = dpool.contiguous().float(), (0, -1, 1)
+        L.call("mgar_bn_act_maxpool_bwd_reduce", dp.data_ptr(), strides[0], strides[1], strides[2], L.fptr(out), _u8ptr(arg),
+               L.fptr(x4), L.fptr(xarg) if xarg is not None else None, b, ck, m, ns, L.fptr(mean2), L.fptr(invstd2),
+               int(ctx.relu2), L.fptr(ws2), L.fptr(dgamma2), L.fptr(dbeta2), L.fptr(coef2), L.fptr(dmask), st)
+        # 2. grad wrt the conv's activated input, W^T dx4, with dx4 formed from x4 in the operand prologue
+        ga = torch.empty_like(x3)
+        L.call("mgar_pointwise_conv_fwd_maxgrad", L.fptr(x4), b, ck, m, ns, L.fptr(w), 1, c, c, L.fptr(mean2), L.fptr(invstd2),
+               L.fptr(gamma2), L.fptr(coef2), _u8ptr(arg), L.fptr(dmask), L.fptr(ga), st)
+        # 3. dW the same way (the X operand keeps its own activation recompute)
+        dw = None
+        if ctx.needs_input_grad[6]:
+            dw = torch.empty_like(w)
+            wsd = torch.empty((max(1, L.raw("mgar_pointwise_dw_workspace_floats", b, c, ck, p)),), dtype=torch.float32, device=dev)
+            L.call("mgar_pointwise_conv_dw_maxgrad", L.fptr(x3), L.fptr(x4), b, c, ck, m, ns, L.fptr(mean), L.fptr(invstd),
+                   L.fptr(gamma), L.fptr(beta), int(ctx.relu), L.fptr(mean2), L.fptr(invstd2), L.fptr(gamma2), L.fptr(coef2),
+                   _u8ptr(arg), L.fptr(dmask), L.fptr(wsd), L.fptr(dw), st)
+        # 4. the inner BatchNorm [+ ReLU] backward, as in _BnActConv
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+        ws = _workspace(x3, b, c, p)
+        if ctx.rowmajor:
+            dx = _bwd_rowmajor(ga, x3, mean, invstd, gamma, beta, ctx.relu, ws, dgamma, dbeta)
+        else:
+            dx = torch.empty_like(x3)
+            L.call("mgar_bn_act_bwd", L.fptr(ga), L.fptr(x3), b, c, p, L.fptr(mean), L.fptr(invstd), L.fptr(gamma),
+                   L.fptr(beta), int(ctx.relu), L.fptr(ws), L.fptr(dgamma), L.fptr(dbeta), L.fptr(dx), st)
+        return dx, dgamma, dbeta, None, None, None, dw, dgamma2, dbeta2, None, None, None, None, None
+
+
 class _PlainConv(Function):
     """y = W x for the FIRST layer of a shared MLP (no BatchNorm in front of it): csrc/pointwise_fwd.hip with the identity in
     place of the activation, so the output is written once at streaming rate and -- when a BatchNorm follows -- the kernel
@@ -309,6 +389,30 @@ def bn_act_conv(x, bn, relu, conv, rowmajor_grad=False, in_stats=None, want_out_
     y = _BnActConv.apply(x3, gamma, beta, mean, invstd, relu, _f32(conv.weight).view(cout, c), rowmajor_grad, out_stats)
     y = y.view(x.shape[0], cout, *x.shape[2:])
     return (y, out_stats) if want_out_stats else y
+
+
+# Backward of the last two layers of a shared MLP without the dense gradient of the max-pool layer (_BnActConvBnMaxPool).  False
+# = the two separate nodes (_BnActConv, _BnActMaxPool), which stay the route of every shape the folded kernels do not take.
+FOLD_MAXPOOL_BWD = True
+
+
+def bn_act_conv_maxpool(x, bn, relu, conv, bn2, relu2, rowmajor_grad=False, in_stats=None):
+    """max over the last axis of relu2?(bn2(conv(relu?(bn(x))))) for x (B, C, M, ns) -> (B, Ck, M) as one autograd node whose
+    backward skips the max-pool layer's dense gradient, or None outside its shapes (the caller then runs bn_act_conv and
+    bn_act_maxpool): fp32, training statistics in both BatchNorms, both channel counts <= 64, ns % 4 == 0, B * M * ns >= 65 536."""
+    if not (FOLD_MAXPOOL_BWD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and torch.is_grad_enabled()
+            and bn.training and bn2.training and conv.bias is None):
+        return None
+    b, c, m, ns = x.shape
+    ck = conv.out_channels
+    if c > FUSED_CONV_MAX_CHANNELS or ck > FUSED_CONV_MAX_CHANNELS or ns % 4 != 0 or ns > 255 or b * m * ns < (1 << 16):
+        return None
+    x3 = x.contiguous().flatten(2)
+    mean, invstd = _stats(x3, bn, in_stats)
+    gamma, beta = _affine(bn, c, x.device)
+    gamma2, beta2 = _affine(bn2, ck, x.device)
+    return _BnActConvBnMaxPool.apply(x3, gamma, beta, mean, invstd, relu, _f32(conv.weight).view(ck, c), gamma2, beta2, bn2, relu2,
+                                     m, ns, rowmajor_grad)
 
 
 def _affine(bn, c, device):

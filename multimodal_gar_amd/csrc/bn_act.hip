@@ -381,7 +381,7 @@ struct DpoolStrides {
 };
 
 // after a fused max-pool only the arg-max element of every group carries gradient:
-// 13 B read per GROUP.  grid (nchunk over B*M, C)
+// 13 B read per GROUP.  grid (nchunk over B*M, C).  dmask (optional): the masked pooled gradient d, 4 B written per group
 template <bool RELU, typename T>
 __global__ __launch_bounds__(BN_THREADS) void bn_max_bwd_partial_kernel(const T *__restrict__ dpool,
                                                                         const T *__restrict__ pooled,
@@ -390,7 +390,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_bwd_partial_kernel(const T 
                                                                         const T *__restrict__ xarg, int B, int C, int M, int NS,
                                                                         const float *__restrict__ mean,
                                                                         const float *__restrict__ invstd,
-                                                                        float *__restrict__ partial, DpoolStrides ds, int chunk) {
+                                                                        float *__restrict__ partial, DpoolStrides ds, int chunk,
+                                                                        float *__restrict__ dmask) {
     __shared__ float scratch[BN_THREADS / 64];
     const int c = blockIdx.y;
     const float mu = mean[c], is = invstd[c];
@@ -403,6 +404,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_bwd_partial_kernel(const T 
         const long long eb = e / M;
         float d = Payload<T>::ld(dpool + eb * ds.b + c * ds.c + (e - eb * M) * ds.m);
         if (RELU && !(Payload<T>::ld(pooled + o) > 0.f)) d = 0.f;
+        if (dmask) dmask[o] = d;   // contiguous (B, C, M): what the gradient-forming GEMM prologues read (mgar_bn_act_maxpool_bwd_reduce)
         const float xh = ((xarg ? Payload<T>::ld(xarg + o) : Payload<T>::ld(x + o * NS + arg[o])) - mu) * is;
         s += d;
         q += d * xh;
@@ -711,6 +713,23 @@ static int bn_act_bwd_impl(const T *dy, const T *x, int B, int C, int P, const f
     return check_launch("bn_act_bwd: launch failed");
 }
 
+// the reduction half of the max-pool backward: partials -> dgamma, dbeta, coef (2 C) = {mean dz, mean dz xhat}; dmask optional
+template <typename T>
+static int bn_act_maxpool_bwd_reduce_impl(const char *who, const T *dpool, const T *pooled, const unsigned char *arg, const T *x,
+                                          const T *xarg, int B, int C, int M, int nsample, const float *mean, const float *invstd,
+                                          int relu, float *workspace, float *dgamma, float *dbeta, float *coef, float *dmask,
+                                          void *stream, const DpoolStrides &ds) {
+    const int chunk = bn_chunk_bwd(C, (long long)B * M), nchunk = (int)(((long long)B * M + chunk - 1) / chunk);
+    hipStream_t st = (hipStream_t)stream;
+    { KtScope kt(KT_BN_MAX_BWD_REDUCE, st, (3.0 * sizeof(T) + 1.0 + (dmask ? 4.0 : 0.0)) * (double)B * C * M);
+    if (relu) hipLaunchKernelGGL((bn_max_bwd_partial_kernel<true, T>), dim3(nchunk, C), dim3(BN_THREADS), 0, st, dpool, pooled, arg, x, xarg, B, C, M, nsample, mean, invstd, workspace, ds, chunk, dmask);
+    else hipLaunchKernelGGL((bn_max_bwd_partial_kernel<false, T>), dim3(nchunk, C), dim3(BN_THREADS), 0, st, dpool, pooled, arg, x, xarg, B, C, M, nsample, mean, invstd, workspace, ds, chunk, dmask);
+    }
+    // the means are over ALL B*M*nsample elements of the channel, not only the arg-max ones
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, st, workspace, nchunk, C, (double)B * M * nsample, dgamma, dbeta, coef);
+    return check_launch(who);
+}
+
 template <typename T>
 static int bn_act_maxpool_bwd_impl(const T *dpool, const T *pooled, const unsigned char *arg, const T *x,
                                    const T *xarg, int B, int C, int M, int nsample, const float *mean, const float *invstd,
@@ -727,12 +746,9 @@ static int bn_act_maxpool_bwd_impl(const T *dpool, const T *pooled, const unsign
     const int chunk = bn_chunk_bwd(C, (long long)B * M), nchunk = (int)(((long long)B * M + chunk - 1) / chunk);
     float *coef = workspace + (size_t)2 * C * nchunk;
     hipStream_t st = (hipStream_t)stream;
-    { KtScope kt(KT_BN_MAX_BWD_REDUCE, st, (3.0 * sizeof(T) + 1.0) * (double)B * C * M);
-    if (relu) hipLaunchKernelGGL((bn_max_bwd_partial_kernel<true, T>), dim3(nchunk, C), dim3(BN_THREADS), 0, st, dpool, pooled, arg, x, xarg, B, C, M, nsample, mean, invstd, workspace, ds, chunk);
-    else hipLaunchKernelGGL((bn_max_bwd_partial_kernel<false, T>), dim3(nchunk, C), dim3(BN_THREADS), 0, st, dpool, pooled, arg, x, xarg, B, C, M, nsample, mean, invstd, workspace, ds, chunk);
-    }
-    // the means are over ALL B*M*nsample elements of the channel, not only the arg-max ones
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, st, workspace, nchunk, C, (double)B * M * nsample, dgamma, dbeta, coef);
+    const int rc = bn_act_maxpool_bwd_reduce_impl<T>("bn_act_maxpool_bwd: launch failed", dpool, pooled, arg, x, xarg, B, C, M, nsample, mean,
+                                                     invstd, relu, workspace, dgamma, dbeta, coef, nullptr, stream, ds);
+    if (rc != MGAR_OK) return rc;
     dim3 grid(B * C, ceil_div((long long)M * nsample, BN_THREADS * ((nsample & 3) == 0 ? 4 : 1)));
     { KtScope kt(KT_BN_MAX_BWD_APPLY, st, (double)B * C * M * (2.0 * sizeof(T) * nsample + 2.0 * sizeof(T) + 1.0));
     if (relu) hipLaunchKernelGGL((bn_max_bwd_apply_kernel<true, T>), grid, dim3(BN_THREADS), 0, st, dpool, pooled, arg, x, C, M, nsample, mean, invstd, gamma, coef, dx, ds);
@@ -888,6 +904,26 @@ MGAR_API int mgar_bn_act_maxpool_bwd_strided(const float *dpool, long long sb, l
     MGAR_REQUIRE(sb >= 0 && sc >= 1 && sm >= 1, "bn_act_maxpool_bwd_strided: bad strides");
     return bn_act_maxpool_bwd_impl<float>(dpool, pooled, arg, x, xarg, B, C, M, nsample, mean, invstd, gamma, relu, workspace, dgamma,
                                           dbeta, dx, stream, sb, sc, sm);
+}
+
+// The reduction half of mgar_bn_act_maxpool_bwd[_strided] alone, for the consumers that form the max-pool layer's gradient in
+// their operand prologue (mgar_pointwise_conv_fwd_maxgrad, mgar_pointwise_conv_dw_maxgrad) instead of reading a dense dx:
+// -> dgamma, dbeta (C), coef (2 C) = per channel {mean dz, mean dz xhat} over all B*M*nsample elements, and dmask (B, C, M)
+// contiguous = dpool zeroed where the ReLU is on and pooled <= 0.  dpool strides as in the strided entry point; sc < 0 =
+// contiguous.  fp32.  workspace: mgar_bn_workspace_floats(B, C, M * nsample) floats.
+MGAR_API int mgar_bn_act_maxpool_bwd_reduce(const float *dpool, long long sb, long long sc, long long sm, const float *pooled,
+                                            const unsigned char *arg, const float *x, const float *xarg, int B, int C, int M,
+                                            int nsample, const float *mean, const float *invstd, int relu, float *workspace,
+                                            float *dgamma, float *dbeta, float *coef, float *dmask, void *stream) {
+    MGAR_REQUIRE(bn_sizes_ok(B, C, (long long)M * nsample) && nsample >= 1 && nsample <= 255, "bn_act_maxpool_bwd_reduce: bad sizes");
+    MGAR_REQUIRE(sc < 0 || (sb >= 0 && sc >= 1 && sm >= 1), "bn_act_maxpool_bwd_reduce: bad dpool strides");
+    if ((long long)B * C * M == 0) return MGAR_OK;
+    const DpoolStrides ds{sc < 0 ? (long long)C * M : sb, sc < 0 ? (long long)M : sc, sc < 0 ? 1 : sm};
+    MGAR_REQUIRE(dpool && pooled && arg && mean && invstd && workspace && coef && dmask, "bn_act_maxpool_bwd_reduce: null pointer");
+    MGAR_REQUIRE(x || xarg, "bn_act_maxpool_bwd_reduce: null pointer");
+    MGAR_REQUIRE(C <= 65535, "bn_act_maxpool_bwd_reduce: C > 65535");
+    return bn_act_maxpool_bwd_reduce_impl<float>("bn_act_maxpool_bwd_reduce: launch failed", dpool, pooled, arg, x, xarg, B, C, M, nsample,
+                                                 mean, invstd, relu, workspace, dgamma, dbeta, coef, dmask, stream, ds);
 }
 
 // Merge groups of G consecutive chunk partials (mean, M2) of a channel into one partial each (Chan et al., in double): the

@@ -42,11 +42,26 @@ struct DwAct {
     int pair;
 };
 
+// GRAD instances: the dY operand is the input gradient of a fused [BatchNorm -> ReLU -> max over ns] layer, formed from that
+// layer's PRE-BN input x4 (B, Cout, M, ns) -- passed as `dy` -- while its rows go from global memory into LDS:
+//   dy[b,o,m,s] = k_o * ((s == arg[b,o,m] ? d[b,o,m] : 0) - m0_o - (x4[b,o,m,s] - mu_o) * is_o * m1_o)
+// in the operation order of bn_max_bwd_apply_kernel (csrc/bn_act.hip), so the staged values are bit for bit the dense
+// gradient that kernel would have written.  ns % 4 == 0: a float4 lies in one group, one arg byte and one d float per float4.
+struct DwGrad {
+    const float *mean, *invstd, *gamma;   // of the max-pool layer's BatchNorm (Cout channels)
+    const float *coef;                    // (Cout, 2) = {m0, m1} (bn_bwd_finalize_kernel)
+    const unsigned char *arg;             // (B, Cout, M)
+    const float *d;                       // (B, Cout, M) pooled gradient, zeroed where the ReLU cut it
+    int M, ns;                            // P = M * ns
+};
+
 // OB x IB output blocks of 32 x 32 per workgroup (OB * IB <= 8)
-template <int OB, int IB>
+template <int OB, int IB, bool GRAD = false>
 __global__ __launch_bounds__(256) void pointwise_dw_kernel(const float *__restrict__ x, const float *__restrict__ dy, int B, int Cin,
-                                                           int Cout, int P, DwAct act, float *__restrict__ partial) {
+                                                           int Cout, int P, DwAct act, float *__restrict__ partial, DwGrad g) {
     extern __shared__ float lds[];                 // [(OB + IB) * 32][DW_LD]
+    constexpr int GR = GRAD ? OB * 32 : 1;
+    __shared__ float g_k[GR], g_m0[GR], g_mu[GR], g_is[GR], g_m1[GR];     // GRAD: per dY row
     __shared__ float act_sc[IB * 32], act_sh[IB * 32], act_mu[IB * 32];   // (x - mu) * sc + sh, as bn_apply_kernel
     __shared__ float act_is[IB * 32];                                     // pair mode: invstd of the row's real channel
     float *sy = lds;                               // dY rows of this workgroup's output blocks
@@ -55,6 +70,19 @@ __global__ __launch_bounds__(256) void pointwise_dw_kernel(const float *__restri
     const bool has_act = act.mean != nullptr;
     const bool pair = act.pair != 0;
     const int CinV = pair ? 2 * Cin : Cin;         // (virtual) input channels = columns of the result
+    if constexpr (GRAD) {
+        for (int r = threadIdx.x; r < OB * 32; r += 256) {
+            const int ch = o_base + r;
+            const bool ok = ch < Cout;
+            const float is = ok ? g.invstd[ch] : 0.f;
+            g_mu[r] = ok ? g.mean[ch] : 0.f;
+            g_is[r] = is;
+            g_k[r] = ok ? (g.gamma ? g.gamma[ch] : 1.f) * is : 0.f;
+            g_m0[r] = ok ? g.coef[2 * ch] : 0.f;
+            g_m1[r] = ok ? g.coef[2 * ch + 1] : 0.f;
+        }
+        if (!has_act) __syncthreads();   // (otherwise the barrier below covers these too)
+    }
     if (has_act) {
         for (int r = threadIdx.x; r < IB * 32; r += 256) {
             const int chv = i_base + r, ch = (pair && chv >= Cin) ? chv - Cin : chv;
@@ -95,9 +123,26 @@ __global__ __launch_bounds__(256) void pointwise_dw_kernel(const float *__restri
     // tile t run; the LDS tile is single-buffered
     constexpr int NV = (OB + IB) * 32 * (DW_TP / 4) / 256;   // float4 per thread and tile
     float4 pre[NV];
+    // GRAD: the dY rows are the first OB * 4 float4 of a thread (row = threadIdx.x / 32 + 8 u); all of them share the column
+    constexpr int NG = GRAD ? OB * 4 : 1;
+    float pre_d[NG];
+    int pre_a[NG], pre_s0 = 0;
     auto fetch = [&](long long tile) {
         const int b = (int)(tile / tiles_per_b);
         const int p0 = (int)(tile - (long long)b * tiles_per_b) * DW_TP;
+        if constexpr (GRAD) {
+            const int p = p0 + (threadIdx.x & 31) * 4;
+            const int m = (int)((unsigned)p / (unsigned)g.ns);   // one 32-bit division per tile
+            pre_s0 = p - m * g.ns;
+#pragma unroll
+            for (int u = 0; u < NG; ++u) {
+                const int ch = o_base + (threadIdx.x >> 5) + 8 * u;
+                const bool ok = ch < Cout && p < P;
+                const size_t go = ((size_t)b * Cout + ch) * g.M + m;
+                pre_d[u] = ok ? g.d[go] : 0.f;
+                pre_a[u] = ok ? (int)g.arg[go] : 0;
+            }
+        }
 #pragma unroll
         for (int u = 0; u < NV; ++u) {
             const int e = threadIdx.x + u * 256;
@@ -125,6 +170,17 @@ __global__ __launch_bounds__(256) void pointwise_dw_kernel(const float *__restri
                 const bool is_y = row < OB * 32;
                 const int ch = is_y ? o_base + row : i_base + row - OB * 32;
                 float4 v = pre[u];
+                if constexpr (GRAD) {
+                    if (u < NG && ch < Cout && p0 + c4 < P) {         // padding stays zero (it is summed over)
+                        const float k = g_k[row], m0 = g_m0[row], mu = g_mu[row], is = g_is[row], m1 = g_m1[row];
+                        const float d = pre_d[u < NG ? u : 0];
+                        const int sa = pre_a[u < NG ? u : 0] - pre_s0;
+                        v.x = k * ((sa == 0 ? d : 0.f) - m0 - (v.x - mu) * is * m1);
+                        v.y = k * ((sa == 1 ? d : 0.f) - m0 - (v.y - mu) * is * m1);
+                        v.z = k * ((sa == 2 ? d : 0.f) - m0 - (v.z - mu) * is * m1);
+                        v.w = k * ((sa == 3 ? d : 0.f) - m0 - (v.w - mu) * is * m1);
+                    }
+                }
                 if (has_act && !is_y && ch < CinV && p0 + c4 < P) {   // padding stays zero
                     const int r = row - OB * 32;
                     if (pair) {
@@ -276,19 +332,19 @@ static void dw_blocks(int Cin, int Cout, int &ob, int &ib) {
     ib = Cin <= 32 ? 1 : (Cin <= 64 ? 2 : 4);        // OB * IB <= 8
 }
 
-template <int OB, int IB>
+template <int OB, int IB, bool GRAD = false>
 static void launch_dw(const float *x, const float *dy, int B, int Cin, int Cout, int P, const DwAct &act, float *partial,
-                      hipStream_t st) {
+                      hipStream_t st, const DwGrad &g = DwGrad{}) {
     static bool attr_set = false;
     const int lds = (OB + IB) * 32 * DW_LD * (int)sizeof(float);
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)pointwise_dw_kernel<OB, IB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute((const void *)pointwise_dw_kernel<OB, IB, GRAD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
     const int CinV = act.pair ? 2 * Cin : Cin;
     const int gy = ceil_div(Cout, OB * 32), gz = ceil_div(CinV, IB * 32);
     const int gx = dw_grid_x(B, CinV, Cout, P, OB, IB);
-    hipLaunchKernelGGL((pointwise_dw_kernel<OB, IB>), dim3((unsigned)gx, gy, gz), dim3(256), lds, st, x, dy, B, Cin, Cout, P, act, partial);
+    hipLaunchKernelGGL((pointwise_dw_kernel<OB, IB, GRAD>), dim3((unsigned)gx, gy, gz), dim3(256), lds, st, x, dy, B, Cin, Cout, P, act, partial, g);
 }
 
 }  // namespace mgar
@@ -338,6 +394,50 @@ MGAR_API int mgar_pointwise_conv_dw(const float *x, const float *dy, int B, int 
                                     int Cout, int P, float *workspace, float *dw,
                                     void *stream) {
     return mgar_pointwise_conv_dw_act(x, dy, B, Cin, Cout, P, nullptr, nullptr, nullptr, nullptr, 0, workspace, dw, stream);
+}
+
+// mgar_pointwise_conv_dw_act for the layer in front of a fused [BatchNorm -> ReLU -> max over nsample], with that max-pool
+// layer's input gradient formed in the dY prologue (GRAD instances) instead of read from memory: x4 (B, Cout, M, nsample) is
+// the max-pool layer's PRE-BN input (= this conv's output); mean / invstd / gamma its BatchNorm's; coef and dmask from
+// mgar_bn_act_maxpool_bwd_reduce.  x (B, Cin, M * nsample) with its own activation as in mgar_pointwise_conv_dw_act.
+// Cin, Cout <= 64, nsample % 4 == 0 (MGAR_EUNSUPPORTED otherwise).  workspace: mgar_pointwise_dw_workspace_floats(B, Cin,
+// Cout, M * nsample) floats.
+MGAR_API int mgar_pointwise_conv_dw_maxgrad(const float *x, const float *x4, int B, int Cin, int Cout, int M, int nsample,
+                                            const float *in_mean, const float *in_invstd, const float *in_gamma,
+                                            const float *in_beta, int in_relu, const float *mean, const float *invstd,
+                                            const float *gamma, const float *coef, const unsigned char *arg, const float *dmask,
+                                            float *workspace, float *dw, void *stream) {
+    MGAR_REQUIRE(B >= 0 && Cin >= 0 && Cout >= 0 && M >= 0 && nsample >= 1 && nsample <= 255, "pointwise_conv_dw_maxgrad: bad sizes");
+    MGAR_REQUIRE((long long)M * nsample <= 2147483647LL - DW_TP, "pointwise_conv_dw_maxgrad: M * nsample too large");
+    if (Cin == 0 || Cout == 0) return MGAR_OK;
+    MGAR_REQUIRE(dw, "pointwise_conv_dw_maxgrad: null pointer");
+    MGAR_REQUIRE(in_mean == nullptr || in_invstd != nullptr, "pointwise_conv_dw_maxgrad: in_mean without in_invstd");
+    if (Cin > 64 || Cout > 64 || (nsample & 3) != 0) {
+        set_error("pointwise_conv_dw_maxgrad: needs Cin <= 64, Cout <= 64 and nsample % 4 == 0 (write the gradient with "
+                  "mgar_bn_act_maxpool_bwd otherwise)");
+        return MGAR_EUNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if ((long long)B * M == 0) {
+        (void)hipMemsetAsync(dw, 0, sizeof(float) * Cout * Cin, st);
+        return check_launch("pointwise_conv_dw_maxgrad: memset failed");
+    }
+    MGAR_REQUIRE(x && x4 && workspace && mean && invstd && coef && arg && dmask, "pointwise_conv_dw_maxgrad: null pointer");
+    const int P = M * nsample;
+    const DwAct act{in_mean, in_invstd, in_gamma, in_beta, in_relu, 0};
+    const DwGrad g{mean, invstd, gamma, coef, arg, dmask, M, nsample};
+    int ob, ib;
+    dw_blocks(Cin, Cout, ob, ib);
+    {
+    KtScope kt(KT_POINTWISE_DW, st, 4.0 * (double)B * P * (Cin + Cout) + 5.0 * (double)B * Cout * M, 2.0 * (double)B * P * Cin * Cout);
+    if (ob == 1 && ib == 1) launch_dw<1, 1, true>(x, x4, B, Cin, Cout, P, act, workspace, st, g);
+    else if (ob == 1) launch_dw<1, 2, true>(x, x4, B, Cin, Cout, P, act, workspace, st, g);
+    else if (ib == 1) launch_dw<2, 1, true>(x, x4, B, Cin, Cout, P, act, workspace, st, g);
+    else launch_dw<2, 2, true>(x, x4, B, Cin, Cout, P, act, workspace, st, g);
+    }
+    const int gx = dw_grid_x(B, Cin, Cout, P, ob, ib), n_out = Cout * Cin;
+    hipLaunchKernelGGL(pointwise_dw_reduce_kernel, dim3(ceil_div(n_out, 64)), dim3(64 * DWR_SLICES), 0, st, workspace, gx, n_out, dw);
+    return check_launch("pointwise_conv_dw_maxgrad: launch failed");
 }
 
 // ---- weight gradient of [BatchNorm -> ReLU -> conv 1x1] AND the reduction of that BatchNorm's backward, in one pass ----------

@@ -23,6 +23,13 @@
 //   * W (<= 32 KB) and the per-channel (sc, sh) sit in LDS, read conflict-free as the A operand;
 //   * every wave owns whole 128-column tiles and software-pipelines them: the loads of the next
 //     16-channel slab are in flight while the MFMAs of the current one run.
+//
+// GRAD operand mode (dX of the layer in front of a fused [BatchNorm -> ReLU -> max over nsample]): the operand is that
+// max-pool layer's input gradient, which is a closed form of data already in memory (bn_max_bwd_apply_kernel, csrc/bn_act.hip)
+//   dx[b,c,m,s] = k_c * ((s == arg[b,c,m] ? d[b,c,m] : 0) - m0_c - (x4[b,c,m,s] - mu_c) * is_c * m1_c)
+// so the kernel reads the PRE-BN tensor x4 (B, C, M, ns) where it would read a dense dx, plus one arg byte and one d float per
+// float4 (ns % 4 == 0: the four columns of a float4 lie in one group), and forms dx while feeding the MFMA, in the operation
+// order of bn_max_bwd_apply_kernel: the products are bit for bit those of the dense route, and dx is never written or re-read.
 #include <type_traits>
 
 #include "common.hpp"
@@ -35,7 +42,15 @@ typedef float __attribute__((ext_vector_type(16))) f32x16;
 constexpr int PF_COLS = 128;  // columns per wave tile
 // channels per slab (2 per MFMA k-step): 16, or 8 for the 64-output-channel instance so that its 128 accumulator
 // registers + two slab buffers stay under 256 VGPRs (2 waves per SIMD instead of 1)
-template <int OB> struct PfSlab { static constexpr int KC = OB == 1 ? 16 : 8; };
+// (4 for its GRAD instance, whose slabs also carry the groups' (d, arg): 8 spilled)
+template <int OB, bool GRAD = false> struct PfSlab { static constexpr int KC = OB == 1 ? 16 : (GRAD ? 4 : 8); };
+
+struct PfGrad {                 // GRAD operand mode: x = x4 (B, Cin, M, ns), P = M * ns
+    const unsigned char *arg;   // (B, Cin, M) arg-max slot of every group
+    const float *d;             // (B, Cin, M) pooled gradient, already zeroed where the ReLU cut it (bn_max_bwd_partial_kernel)
+    const float *coef;          // (Cin, 2) = {m0, m1} of the BatchNorm backward (bn_bwd_finalize_kernel)
+    int M, ns;
+};
 
 template <typename T>
 struct PfArgs {
@@ -50,20 +65,40 @@ struct PfArgs {
     // bn_partial_kernel with chunk = 128 -- stats[(o * ntiles + tile) * 2 + {0, 1}], tile = b * (P / 128) + tile of the
     // sample -- so that the BatchNorm that follows needs no pass over y for its statistics (csrc/bn_act.hip, bn_finalize_kernel)
     float *stats;
+    PfGrad g;        // GRAD instances only (mean / invstd / gamma are then those of the max-pool layer's BatchNorm)
 };
 
-template <int OB, typename T, bool STATS = false>
+// one slab of operand registers; the GRAD instances carry the group's (d, arg) next to every float4 and the float4's first slot
+template <int KS, bool GRAD> struct PfBuf { float4 v[KS]; };
+template <int KS> struct PfBuf<KS, true> { float4 v[KS]; float d[KS]; int a[KS]; int s0; };
+
+template <int OB, typename T, bool STATS = false, bool GRAD = false>
 __global__ __launch_bounds__(256, 2) void pointwise_fwd_kernel(PfArgs<T> a) {
-    constexpr int PF_KC = PfSlab<OB>::KC, KS = PF_KC / 2;
+    constexpr int PF_KC = PfSlab<OB, GRAD>::KC, KS = PF_KC / 2;
     constexpr int WLD = OB == 1 ? 32 : 96;  // LDS row stride of W: the two half-waves hit disjoint banks
-    extern __shared__ float lds[];          // [nkc*16][WLD] weights, then [nkc*16][4] (sc, sh, mu, -)
+    extern __shared__ float lds[];          // [nkc*16][WLD] weights, then [nkc*16][4] (sc, sh, mu, -); GRAD: (k, m0, mu, is), then [nkc*16] m1
     const int nkc = (a.Cin + PF_KC - 1) / PF_KC;
     float *wl = lds;
     float *act = lds + (size_t)nkc * PF_KC * WLD;
+    float *gm1 = act + (size_t)nkc * PF_KC * 4;
     for (int e = threadIdx.x; e < nkc * PF_KC * WLD; e += 256) {
         const int ch = e / WLD, o = e - ch * WLD;
         wl[e] = (ch < a.Cin && o < a.Cout) ? a.w[(size_t)o * a.w_rs + (size_t)ch * a.w_cs] : 0.f;
     }
+    if constexpr (GRAD) {
+        for (int ch = threadIdx.x; ch < nkc * PF_KC; ch += 256) {
+            float k = 0.f, m0 = 0.f, mu = 0.f, is = 0.f, m1 = 0.f;   // padding channels: the operand comes out as zero
+            if (ch < a.Cin) {
+                mu = a.mean[ch];
+                is = a.invstd[ch];
+                k = (a.gamma ? a.gamma[ch] : 1.f) * is;
+                m0 = a.g.coef[2 * ch];
+                m1 = a.g.coef[2 * ch + 1];
+            }
+            *reinterpret_cast<float4 *>(act + 4 * ch) = make_float4(k, m0, mu, is);
+            gm1[ch] = m1;
+        }
+    } else
     for (int ch = threadIdx.x; ch < nkc * PF_KC; ch += 256) {
         float sc = 1.f, sh = 0.f, mu = 0.f;   // act(v) = (v - mu) * sc + sh: the arithmetic of bn_apply_kernel
         if (a.mean && ch < a.Cin) {
@@ -94,7 +129,8 @@ __global__ __launch_bounds__(256, 2) void pointwise_fwd_kernel(PfArgs<T> a) {
             for (int r = 0; r < 16; ++r) acc[ob][j][r] = 0.f;
 
     // slab loads of step s (tile s / nkc of this wave, channel slab s % nkc)
-    auto issue = [&](long long s, float4 (&buf)[KS]) {
+    auto issue = [&](long long s, PfBuf<KS, GRAD> &sl) {
+        float4 (&buf)[KS] = sl.v;
         const long long t = wave_id + (s / nkc) * nwaves;
         const int kc = (int)(s % nkc);
         const int b = (int)(t / tiles_per_b);
@@ -106,13 +142,35 @@ __global__ __launch_bounds__(256, 2) void pointwise_fwd_kernel(PfArgs<T> a) {
             buf[ks] = (ch < a.Cin && p < a.P) ? Payload<T>::ld4(src + (size_t)2 * ks * a.P)
                                               : make_float4(0.f, 0.f, 0.f, 0.f);
         }
+        if constexpr (GRAD) {   // one 32-bit division per slab: every float4 of the slab lies in group m of its channel
+            const int m = (int)((unsigned)p / (unsigned)a.g.ns);
+            sl.s0 = p - m * a.g.ns;
+            const size_t go = ((size_t)b * a.Cin + kc * PF_KC + h) * a.g.M + m;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const bool ok = kc * PF_KC + 2 * ks + h < a.Cin && p < a.P;
+                sl.d[ks] = ok ? a.g.d[go + (size_t)2 * ks * a.g.M] : 0.f;
+                sl.a[ks] = ok ? (int)a.g.arg[go + (size_t)2 * ks * a.g.M] : 0;
+            }
+        }
     };
-    auto compute = [&](long long s, float4 (&buf)[KS]) {
+    auto compute = [&](long long s, PfBuf<KS, GRAD> &sl) {
+        float4 (&buf)[KS] = sl.v;
         const int kc = (int)(s % nkc);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int ch = kc * PF_KC + 2 * ks + h;
             float4 v = buf[ks];
+            if constexpr (GRAD) {   // bn_max_bwd_apply_kernel's expression, term for term (columns past P are never stored)
+                const float4 ac = *reinterpret_cast<const float4 *>(act + 4 * ch);
+                const float k = ac.x, m0 = ac.y, mu = ac.z, is = ac.w, m1 = gm1[ch];
+                const float d = sl.d[ks];
+                const int sa = sl.a[ks] - sl.s0;   // the arg-max slot relative to the float4's first column
+                v.x = k * ((sa == 0 ? d : 0.f) - m0 - (v.x - mu) * is * m1);
+                v.y = k * ((sa == 1 ? d : 0.f) - m0 - (v.y - mu) * is * m1);
+                v.z = k * ((sa == 2 ? d : 0.f) - m0 - (v.z - mu) * is * m1);
+                v.w = k * ((sa == 3 ? d : 0.f) - m0 - (v.w - mu) * is * m1);
+            } else
             if (has_act) {
                 const float4 ac = *reinterpret_cast<const float4 *>(act + 4 * ch);
                 const float sc = ac.x, sh = ac.y, mu = ac.z;
@@ -165,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_fwd_kernel(PfArgs<T> a) {
         }
     };
 
-    float4 buf0[KS], buf1[KS];
+    PfBuf<KS, GRAD> buf0, buf1;
     issue(0, buf0);
     for (long long s = 0; s < steps; s += 2) {
         if (s + 1 < steps) issue(s + 1, buf1);
@@ -177,20 +235,20 @@ __global__ __launch_bounds__(256, 2) void pointwise_fwd_kernel(PfArgs<T> a) {
     }
 }
 
-template <int OB, typename T, bool STATS = false>
+template <int OB, typename T, bool STATS = false, bool GRAD = false>
 static void launch_pf(const PfArgs<T> &a, hipStream_t st) {
-    constexpr int WLD = OB == 1 ? 32 : 96, PF_KC = PfSlab<OB>::KC;
+    constexpr int WLD = OB == 1 ? 32 : 96, PF_KC = PfSlab<OB, GRAD>::KC;
     const int nkc = (a.Cin + PF_KC - 1) / PF_KC;
-    const int lds = nkc * PF_KC * (WLD + 4) * (int)sizeof(float);
+    const int lds = nkc * PF_KC * (WLD + 4 + (GRAD ? 1 : 0)) * (int)sizeof(float);
     static int attr_lds = 0;
     if (lds > 65536 && lds > attr_lds) {
-        (void)hipFuncSetAttribute((const void *)pointwise_fwd_kernel<OB, T, STATS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute((const void *)pointwise_fwd_kernel<OB, T, STATS, GRAD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_lds = lds;
     }
     const long long ntiles = (long long)a.B * ((a.P + PF_COLS - 1) / PF_COLS);
     long long wgs = (ntiles + 3) / 4;
     if (wgs > 2048) wgs = 2048;   // 8 workgroups per CU; waves stride over the tiles
-    hipLaunchKernelGGL((pointwise_fwd_kernel<OB, T, STATS>), dim3((unsigned)wgs), dim3(256), lds, st, a);
+    hipLaunchKernelGGL((pointwise_fwd_kernel<OB, T, STATS, GRAD>), dim3((unsigned)wgs), dim3(256), lds, st, a);
 }
 
 }  // namespace mgar
@@ -247,4 +305,31 @@ MGAR_API int mgar_pointwise_conv_fwd_stats(const float *x, int B, int Cin, int P
     }
     return pointwise_conv_fwd_impl<float>(x, B, Cin, P, w, w_row_stride, w_col_stride, Cout, in_mean, in_invstd, in_gamma, in_beta,
                                           in_relu, y, stream, out_stats);
+}
+
+// dX of the layer in front of a fused [BatchNorm -> ReLU -> max over nsample], with that max-pool layer's input gradient formed
+// in the operand prologue instead of read from memory (GRAD mode above):
+//   y[b, o, p] = sum_i w[o * w_row_stride + i * w_col_stride] * dx4[b, i, p]
+//   dx4[b,i,m,s] = k_i * ((s == arg[b,i,m] ? dmask[b,i,m] : 0) - coef[2i] - (x4[b,i,m,s] - mean_i) * invstd_i * coef[2i+1]),  k_i = gamma_i invstd_i
+// x4 (B, Cin, M, nsample) is the max-pool layer's PRE-BN input; coef and dmask come from mgar_bn_act_maxpool_bwd_reduce.
+// Cin, Cout <= 64, nsample % 4 == 0 (MGAR_EUNSUPPORTED otherwise).  fp32.
+MGAR_API int mgar_pointwise_conv_fwd_maxgrad(const float *x4, int B, int Cin, int M, int nsample, const float *w, int w_row_stride,
+                                             int w_col_stride, int Cout, const float *mean, const float *invstd, const float *gamma,
+                                             const float *coef, const unsigned char *arg, const float *dmask, float *y, void *stream) {
+    MGAR_REQUIRE(B >= 0 && Cin >= 0 && Cout >= 0 && M >= 0 && nsample >= 1 && nsample <= 255, "pointwise_conv_fwd_maxgrad: bad sizes");
+    MGAR_REQUIRE((long long)M * nsample <= 2147483647LL - PF_COLS, "pointwise_conv_fwd_maxgrad: M * nsample too large");
+    if ((long long)B * M == 0 || Cout == 0) return MGAR_OK;
+    MGAR_REQUIRE(x4 && w && y && mean && invstd && coef && arg && dmask, "pointwise_conv_fwd_maxgrad: null pointer");
+    if (Cout > 64 || Cin > 64 || Cin == 0 || (nsample & 3) != 0) {
+        set_error("pointwise_conv_fwd_maxgrad: needs 1 <= Cin <= 64, Cout <= 64 and nsample % 4 == 0 (write the gradient with "
+                  "mgar_bn_act_maxpool_bwd otherwise)");
+        return MGAR_EUNSUPPORTED;
+    }
+    const int P = M * nsample;
+    PfArgs<float> a{x4, w, mean, invstd, gamma, nullptr, y, B, Cin, Cout, P, w_row_stride, w_col_stride, 0, nullptr, {arg, dmask, coef, M, nsample}};
+    hipStream_t st = (hipStream_t)stream;
+    KtScope kt(KT_POINTWISE_FWD, st, 4.0 * (double)B * P * (Cin + Cout) + 5.0 * (double)B * Cin * M, 2.0 * (double)B * P * Cin * Cout);
+    if (Cout <= 32) launch_pf<1, float, false, true>(a, st);
+    else launch_pf<2, float, false, true>(a, st);
+    return check_launch("pointwise_conv_fwd_maxgrad: launch failed");
 }

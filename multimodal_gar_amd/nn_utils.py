@@ -107,6 +107,16 @@ class PointwiseSequential(nn.Sequential):
                 last = i + (2 if relu else 1) >= n
                 y = None
                 nxt = i + (2 if relu else 1)
+                if nxt < n and _is_pointwise(layers[nxt]) and self.fuse_bn_conv and pool_last and x.dim() == 4 \
+                        and nxt + 1 < n and isinstance(layers[nxt + 1], _BN_TYPES):
+                    # [BN -> ReLU -> conv -> BN -> ReLU -> max over ns] at the end of the MLP: one node, whose backward forms
+                    # the max-pool layer's gradient inside the conv's dX / dW kernels instead of writing it (bn_ops)
+                    relu2 = nxt + 2 < n and isinstance(layers[nxt + 2], nn.ReLU)
+                    if nxt + (3 if relu2 else 2) >= n:
+                        y = bn_ops.bn_act_conv_maxpool(x, layer, relu, layers[nxt], layers[nxt + 1], relu2, rowmajor_grad=rm,
+                                                       in_stats=stats)
+                        if y is not None:
+                            return y, True
                 if nxt < n and _is_pointwise(layers[nxt]) and self.fuse_bn_conv:
                     # [BN -> ReLU -> next conv] in one pass; the activated tensor is never written.  If a BatchNorm follows that
                     # conv, the kernel also leaves the statistics partials of its output (no statistics pass over it)
