@@ -339,7 +339,10 @@ int mgar_rowmajor_dw(const float *a, int lda, const float *f, int ldf, long long
  *                 xarg (B,C,M, may be NULL) = x at the arg-max (lets the backward reduction read
  *                 coalesced arrays; act_maxpool_bwd gathers from x when it is NULL)
  *   act_bwd     : dx, dgamma, dbeta of y = [relu](bn_train(x)) given dy (all fully written)
- *   act_maxpool_bwd : the same when y was reduced by act_maxpool_fwd (dpool, pooled, arg) */
+ *   act_maxpool_bwd : the same when y was reduced by act_maxpool_fwd (dpool, pooled, arg)
+ * Non-finite values: the FORWARD entry points (act_fwd*, act_small, act_maxpool_fwd) propagate NaN as torch.relu and
+ * torch.max do: a NaN activation gives a NaN output, a group that holds one a NaN maximum with arg on the first NaN.  The
+ * BACKWARD masks are plain comparisons (`pre > 0`, `pooled > 0`): a NaN there passes no gradient. */
 int mgar_bn_workspace_floats(int B, int C, int P);
 int mgar_bn_train_stats(const float *x, int B, int C, int P, float eps, float momentum, float *workspace,
                         float *mean, float *invstd, float *running_mean, float *running_var,

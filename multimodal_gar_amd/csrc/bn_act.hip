@@ -38,6 +38,12 @@ __device__ __forceinline__ float block_sum(float v, float *scratch) {
     return t;
 }
 
+// ReLU and the max scan PROPAGATE NaN as torch.relu / torch.max do (fmaxf(NaN, 0) is 0 and NaN > best is false: a diverged
+// channel would come out as zeros).  Compare-selects: a NaN fails every comparison.
+__device__ __forceinline__ float relu_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
+// true when a replaces best in a running maximum: a > best, or a is the first NaN
+__device__ __forceinline__ bool max_takes(float a, float best) { return !(a <= best) && best == best; }
+
 // element e of channel c (0 <= e < B*P) lives at ((e / P) * C + c) * P + e % P
 __device__ __forceinline__ size_t chan_off(long long e, int c, int C, int P) {
     const long long b = e / P;
@@ -169,7 +175,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_small_fused_kernel(const T *__r
         }
     }
     __syncthreads();                                     // block_sum reuses its scratch
-    const float var = fmaxf(block_sum(q, scratch) / (float)n, 0.f);
+    float var = block_sum(q, scratch) / (float)n;
+    if (var < 0.f) var = 0.f;                            // a compare: a NaN variance (a NaN or an inf in the channel) stays NaN
     const float is = (float)(1.0 / sqrt((double)var + (double)eps));
     if (threadIdx.x == 0) {
         if (mean_out) mean_out[row] = mu;
@@ -188,7 +195,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_small_fused_kernel(const T *__r
         if (e < n) {
             float4 r = v[u];
             r.x = (r.x - mu) * sc + sh; r.y = (r.y - mu) * sc + sh; r.z = (r.z - mu) * sc + sh; r.w = (r.w - mu) * sc + sh;
-            if (RELU) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+            if (RELU) { r.x = relu_nan(r.x); r.y = relu_nan(r.y); r.z = relu_nan(r.z); r.w = relu_nan(r.w); }
             size_t o;
             if (per_sample) {
                 o = (size_t)(row / C) * y_bstride + (size_t)c * P + e;
@@ -227,14 +234,14 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
             if (p < P) {
                 float4 v = Payload<T>::ld4(xr + p);
                 v.x = (v.x - mu) * sc + sh; v.y = (v.y - mu) * sc + sh; v.z = (v.z - mu) * sc + sh; v.w = (v.w - mu) * sc + sh;
-                if (RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                if (RELU) { v.x = relu_nan(v.x); v.y = relu_nan(v.y); v.z = relu_nan(v.z); v.w = relu_nan(v.w); }
                 Payload<T>::st4(yr + p, v);
             }
         }
     } else {
         for (int p = base + threadIdx.x; p < min(P, base + BN_THREADS * 4 * BN_APPLY_V); p += BN_THREADS) {
             float v = (Payload<T>::ld(xr + p) - mu) * sc + sh;
-            Payload<T>::st(yr + p, RELU ? fmaxf(v, 0.f) : v);
+            Payload<T>::st(yr + p, RELU ? relu_nan(v) : v);
         }
     }
 }
@@ -245,7 +252,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
 // NS/4 lanes that share a group combine their (value, index) pairs with an xor butterfly on the DPP
 // crossbar (quad_perm, row_half_mirror, row_mirror).  grid (rows, ceil(M*NS/4 / 256))
 __device__ __forceinline__ void max_pair(float &v, int &i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+    // equal values, or two NaNs: the smaller index, so that both lanes of a pair end with the same (value, index)
+    if (max_takes(ov, v) || ((ov == v || (ov != ov && v != v)) && oi < i)) { v = ov; i = oi; }
 }
 
 template <int CTRL>
@@ -287,7 +295,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_vec_kernel(const T *__restr
             const float a[4] = {(v[u].x - mu) * sc + sh, (v[u].y - mu) * sc + sh, (v[u].z - mu) * sc + sh, (v[u].w - mu) * sc + sh};
 #pragma unroll
             for (int w = 0; w < 4; ++w)
-                if (a[w] > best) { best = a[w]; bi = s0 + w; }
+                if (max_takes(a[w], best)) { best = a[w]; bi = s0 + w; }
         }
         if (G >= 2) dpp_max_step<0xB1>(best, bi);    // quad_perm [1,0,3,2]  (xor 1)
         if (G >= 4) dpp_max_step<0x4E>(best, bi);    // quad_perm [2,3,0,1]  (xor 2)
@@ -295,7 +303,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_vec_kernel(const T *__restr
         if (G >= 16) dpp_max_step<0x140>(best, bi);  // row_mirror           (acts as xor 8)
         if (live && (threadIdx.x & (G - 1)) == 0) {
             const long long m = q / G;
-            Payload<T>::st(out + (size_t)row * M + m, RELU ? fmaxf(best, 0.f) : best);
+            Payload<T>::st(out + (size_t)row * M + m, RELU ? relu_nan(best) : best);
             arg[(size_t)row * M + m] = (unsigned char)bi;
             // the pre-BN value at the arg-max (the line was just read: an L1/L2 hit), so that the backward
             // reduction reads three coalesced (B,C,M) arrays instead of gathering one element per group
@@ -322,9 +330,9 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_kernel(const T *__restrict_
     int bi = 0;
     for (int s = 0; s < NS; ++s) {
         const float a = (Payload<T>::ld(xr + s) - mu) * sc + sh;
-        if (a > best) { best = a; bi = s; }
+        if (max_takes(a, best)) { best = a; bi = s; }
     }
-    Payload<T>::st(out + (size_t)row * M + m, RELU ? fmaxf(best, 0.f) : best);
+    Payload<T>::st(out + (size_t)row * M + m, RELU ? relu_nan(best) : best);
     arg[(size_t)row * M + m] = (unsigned char)bi;
     if (xarg) xarg[(size_t)row * M + m] = xr[bi];
 }
@@ -602,8 +610,9 @@ static int bn_act_fwd_impl(const T *x, int B, int C, int P, const float *mean, c
     MGAR_REQUIRE(bn_sizes_ok(B, C, P), "bn_act_fwd: bad sizes");
     if (y_bstride < 0) y_bstride = (long long)C * P;
     MGAR_REQUIRE(y_bstride >= (long long)C * P, "bn_act_fwd: output batch stride smaller than a sample");
-    MGAR_REQUIRE((P & 3) != 0 || ((y_bstride * (long long)sizeof(T)) % 16 == 0 && (uintptr_t)y % 16 == 0),
-                 "bn_act_fwd: output slice not 16-byte aligned");
+    // four elements per load / store: 16 bytes of fp32, 8 of bf16 (a contiguous bf16 y with C * P = 12 is a legal slice)
+    MGAR_REQUIRE((P & 3) != 0 || (y_bstride % 4 == 0 && (uintptr_t)y % (4 * sizeof(T)) == 0),
+                 "bn_act_fwd: output slice not aligned to four elements");
     if ((long long)B * C * P == 0) return MGAR_OK;
     MGAR_REQUIRE(x && y && mean && invstd, "bn_act_fwd: null pointer");
     MGAR_REQUIRE((long long)P <= 65535LL * BN_THREADS * 4, "bn_act_fwd: P too large");
@@ -809,8 +818,8 @@ static int bn_act_small_impl(const T *x, int B, int C, int P, int per_sample, fl
     }
     MGAR_REQUIRE(x && y, "bn_act_small: null pointer");
     if (y_bstride < 0) y_bstride = (long long)C * P;
-    MGAR_REQUIRE(y_bstride >= (long long)C * P && (y_bstride * (long long)sizeof(T)) % 16 == 0 && (uintptr_t)y % 16 == 0,
-                 "bn_act_small: bad output slice");
+    MGAR_REQUIRE(y_bstride >= (long long)C * P && y_bstride % 4 == 0 && (uintptr_t)y % (4 * sizeof(T)) == 0,
+                 "bn_act_small: bad output slice");   // four elements per store: 16 bytes of fp32, 8 of bf16
     const int rows = per_sample ? B * C : C;
     const bool track = running_mean || running_var || num_batches_tracked;
     MGAR_REQUIRE(!(per_sample && track) || (workspace && mean), "bn_act_small: per-sample running update needs workspace and mean");

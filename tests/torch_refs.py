@@ -352,3 +352,197 @@ def qg_final_stats_bounds(y, eps, chunk=128):
     assert (low > 0).all()
     invstd = (var + eps) ** -0.5
     return dmean_t.mean(1) + U32 * mean.abs() + TINY32, 0.5 * dvar * low ** -1.5 + U32 * invstd
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# BatchNorm(train) + ReLU + max over nsample (csrc/bn_act.hip): float64 references in numpy and the rounding-count bounds of
+# DESIGN.md section 5c.  gamma_u(j) = j u / (1 - j u) bounds (1 + u)^j - 1.
+def gamma_u(j):
+    return j * U32 / (1.0 - j * U32)
+
+
+def bn_chunk(B, C, P):
+    """Elements per workgroup of the statistics / backward reductions: bn_chunk() of bn_act.hip restated."""
+    n, chunk = B * P, 65536
+    while chunk > 4096 and -(-n // chunk) * C < 2048:
+        chunk >>= 1
+    return chunk
+
+
+def bn_channel_major(x):
+    """(B, C, P) -> float64 (C, B * P): the element order of a channel."""
+    x = np.asarray(x, np.float64)
+    return np.ascontiguousarray(x.transpose(1, 0, 2)).reshape(x.shape[1], -1)
+
+
+def bn_stats_ref(x):
+    """x (B, C, P) -> float64 (mean (C), biased variance (C))."""
+    xc = bn_channel_major(x)
+    mean = xc.mean(1)
+    return mean, ((xc - mean[:, None]) ** 2).mean(1)
+
+
+def bn_running_ref(means, variances, n, momentum, running_mean, running_var, dmean=None, dvar=None, roundings=6):
+    """The momentum updates of rows g = 0.. of means / biased variances (G, C) in order, unbiased correction n / (n - 1) for
+    n > 1, with the fp32 values of momentum and 1 - momentum the kernels use -> float64 (running_mean, running_var, bound,
+    bound).  A step rounds each of its two terms at most `roundings` times (scaling, the unbiased factor in fp32 in the
+    one-launch kernel, the addition) and carries the statistics' own bounds dmean / dvar (G, C) scaled by momentum."""
+    means, variances = np.atleast_2d(np.asarray(means, np.float64)), np.atleast_2d(np.asarray(variances, np.float64))
+    mom, om = float(np.float32(momentum)), float(np.float32(1.0) - np.float32(momentum))
+    k = n / (n - 1.0) if n > 1 else 1.0
+    rm, rv = np.asarray(running_mean, np.float64).copy(), np.asarray(running_var, np.float64).copy()
+    brm, brv = np.zeros_like(rm), np.zeros_like(rv)
+    zero = np.zeros_like(means)
+    dmean, dvar = (zero if dmean is None else np.atleast_2d(dmean)), (zero if dvar is None else np.atleast_2d(dvar))
+    for g in range(means.shape[0]):
+        brm = om * brm + mom * dmean[g] + roundings * U32 * (np.abs(om * rm) + np.abs(mom * means[g])) + TINY32
+        brv = om * brv + mom * k * dvar[g] + roundings * U32 * (np.abs(om * rv) + np.abs(mom * k * variances[g])) + TINY32
+        rm = om * rm + mom * means[g]
+        rv = om * rv + mom * k * variances[g]
+    return rm, rv, brm, brv
+
+
+def _per_channel(a, B, C, per_sample):
+    return np.asarray(a, np.float64).reshape((B, C, 1) if per_sample else (1, C, 1))
+
+
+def bn_apply_ref(x, mean, invstd, gamma, beta, relu, per_sample=False):
+    """y = [relu]((x - mean) * invstd * gamma + beta) in float64 of the given (fp32) mean / invstd (C, or B * C with
+    per-sample statistics) -> (pre-activation, y, bound).  bound = 4 u (|x - mean| |sc| + |pre|) + 2^-149: x - mean,
+    sc = invstd * gamma, the product (three roundings on the first term), the addition (one on the sum); a ReLU is
+    1-Lipschitz and adds nothing."""
+    x = np.asarray(x, np.float64)
+    B, C, _ = x.shape
+    mu, inv = _per_channel(mean, B, C, per_sample), _per_channel(invstd, B, C, per_sample)
+    g = np.ones(C) if gamma is None else np.asarray(gamma, np.float64)
+    b = np.zeros(C) if beta is None else np.asarray(beta, np.float64)
+    sc = inv * g.reshape(1, C, 1)
+    pre = (x - mu) * sc + b.reshape(1, C, 1)
+    bound = 4.0 * U32 * (np.abs(x - mu) * np.abs(sc) + np.abs(pre)) + TINY32
+    return pre, (np.maximum(pre, 0.0) if relu else pre), bound
+
+
+def bn_max_ref(pre, relu):
+    """pre (B, C, M, ns) float64 -> (max over ns [after ReLU], FIRST arg-max of the pre-ReLU values)."""
+    arg = np.argmax(pre, axis=-1)                     # numpy: the first occurrence
+    best = np.take_along_axis(pre, arg[..., None], -1)[..., 0]
+    return (np.maximum(best, 0.0) if relu else best), arg
+
+
+def bn_bwd_ref(dz, x, mean, invstd, gamma, n=None):
+    """Closed-form backward of y = bn_train(x) * gamma + beta given dz = the gradient behind the ReLU mask, all (B, C, P),
+    in float64 of the given mean / invstd: dbeta = sum dz, dgamma = sum dz xh, coef = (dbeta, dgamma) / n,
+    dx = invstd gamma (dz - coef0 - xh coef1).  -> dict with those and the absolute sums the bounds need."""
+    dz, x = np.asarray(dz, np.float64), np.asarray(x, np.float64)
+    B, C, P = x.shape
+    n = B * P if n is None else n
+    mu, inv = _per_channel(mean, B, C, False), _per_channel(invstd, B, C, False)
+    g = np.ones(C) if gamma is None else np.asarray(gamma, np.float64)
+    xh = (x - mu) * inv
+    dbeta, dgamma = dz.sum((0, 2)), (dz * xh).sum((0, 2))
+    coef = np.stack([dbeta, dgamma], 1) / n
+    k = inv * g.reshape(1, C, 1)
+    dx = k * (dz - coef[:, 0].reshape(1, C, 1) - xh * coef[:, 1].reshape(1, C, 1))
+    return dict(dbeta=dbeta, dgamma=dgamma, coef=coef, dx=dx, xh=xh, k=k, dz=dz, n=n,
+                sabs_beta=np.abs(dz).sum((0, 2)), sabs_gamma=np.abs(dz * xh).sum((0, 2)))
+
+
+def bn_bwd_bounds(r, longest_lane_chain, coef_given=False):
+    """Bounds of dbeta, dgamma, coef and dx for a bn_bwd_ref result.  longest_lane_chain = additions a lane makes before the
+    64-lane tree (6) and the 4-wave sum (3): a term of dbeta passes depth = chain + 9 roundings, a term of dgamma three
+    more (x - mean, * invstd, * dz); the chunks are summed in double and rounded once.  dx = k (d - m0 - xh m1): k, x - mean,
+    * invstd, * m1, d - m0, the difference, * k: at most 7 roundings on a term, plus the bounds of m0, m1 scaled by |k|,
+    |k xh| (0 when the caller supplies coef)."""
+    depth = longest_lane_chain + 9
+    bbeta = gamma_u(depth) * r["sabs_beta"] + U32 * np.abs(r["dbeta"]) + TINY32
+    bgamma = gamma_u(depth + 3) * r["sabs_gamma"] + U32 * np.abs(r["dgamma"]) + TINY32
+    bcoef = np.stack([bbeta, bgamma], 1) / r["n"] + U32 * np.abs(r["coef"]) + TINY32
+    if coef_given:
+        bcoef = np.zeros_like(bcoef)
+    C = r["coef"].shape[0]
+    m0, m1 = r["coef"][:, 0].reshape(1, C, 1), r["coef"][:, 1].reshape(1, C, 1)
+    ak = np.abs(r["k"])
+    bdx = gamma_u(7) * ak * (np.abs(r["dz"]) + np.abs(m0) + np.abs(r["xh"] * m1)) \
+        + (1.0 + gamma_u(7)) * ak * (bcoef[:, 0].reshape(1, C, 1) + np.abs(r["xh"]) * bcoef[:, 1].reshape(1, C, 1)) + TINY32
+    return bbeta, bgamma, bcoef, bdx
+
+
+def bn_chan_merge_ref(cnt, mean_k, m2_k):
+    """Chan et al.: chunks of cnt (K) elements with means / sums of squared deviations (C, K) -> float64 (mean, M2) (C)."""
+    cnt, mean_k, m2_k = (np.asarray(a, np.float64) for a in (cnt, mean_k, m2_k))
+    mean = (cnt * mean_k).sum(1) / cnt.sum()
+    return mean, m2_k.sum(1) + (cnt * (mean_k - mean[:, None]) ** 2).sum(1)
+
+
+def bn_partial_stats_bounds(xc, chunk, vec):
+    """What bn_partial_kernel leaves per (channel, chunk) of xc (C, n) float64, and how far off it may be:
+    (cnt (K), mean_k, M2_k, dmean_k, dM2_k (C, K)).  Per chunk of nk elements, with p the mean of its first min(256, nk)
+    elements (the pivot; the kernel's fp32 p_hat is within dp = gamma_u(10) mean|first elements| of it: 6 + 3 additions, the
+    division) and L = ceil(nk / 256 [/ 4 with float4 loads]) additions per lane:
+      s = sum (x - p_hat): x - p_hat (1 rounding), the float4's pair tree (2), L, the 64-lane tree (6), 4 waves (3):
+          |ds| <= gamma_u(L + 12) * A1,  A1 = sum (|x - p| + dp);
+      chunk mean = p_hat + s / nk in double, rounded once:  dmean = |ds| / nk + u |mean_k|;
+      q = sum (x - p_hat)^2: two more roundings per term: |dq| <= gamma_u(L + 14) * A2,  A2 = sum (|x - p| + dp)^2;
+      M2 = q - s^2 / nk in double, rounded once:  dM2 = |dq| + (2 |s| |ds| + ds^2) / nk + u M2,  |s| <= nk (|mean_k - p| + dp).
+    Nothing here grows with |mean| but u |mean_k| (and dp, which enters squared or times u)."""
+    C, n = xc.shape
+    out = []
+    for e0 in range(0, n, chunk):
+        v = xc[:, e0:e0 + chunk]
+        nk = v.shape[1]
+        npiv = min(256, nk)
+        p = v[:, :npiv].mean(1, keepdims=True)
+        dp = gamma_u(10) * np.abs(v[:, :npiv]).mean(1, keepdims=True)
+        L = -(-nk // (256 * (4 if vec else 1)))
+        dev_ = np.abs(v - p) + dp
+        a1, a2 = dev_.sum(1), (dev_ ** 2).sum(1)
+        mean_k = v.mean(1)
+        m2_k = ((v - mean_k[:, None]) ** 2).sum(1)
+        ds = gamma_u(L + 12) * a1
+        s_abs = nk * (np.abs(mean_k - p[:, 0]) + dp[:, 0])
+        dmean = ds / nk + U32 * np.abs(mean_k) + TINY32
+        dm2 = gamma_u(L + 14) * a2 + (2.0 * s_abs * ds + ds * ds) / nk + U32 * m2_k + TINY32
+        out.append((float(nk), mean_k, m2_k, dmean, dm2))
+    cnt = np.array([o[0] for o in out])
+    return (cnt,) + tuple(np.stack([o[i] for o in out], 1) for i in (1, 2, 3, 4))
+
+
+def bn_merge_bounds(cnt, mean_k, m2_k, dmean_k, dm2_k, eps):
+    """bn_finalize_kernel: Chan's merge in double of partials that are within dmean_k / dM2_k of the true ones, one fp32
+    rounding each of mean and invstd -> float64 (mean, var, mean bound, invstd bound, var bound), as qg_final_stats_bounds:
+      |d mean| <= sum n_k dmean_k / n + u |mean|;
+      |d var|  <= [sum dM2_k + sum n_k (4 d |mean_k - mean| + 4 d^2)] / n,  d = max_k dmean_k (both means move by <= d);
+      |d invstd| <= |d var| / 2 (var + eps - |d var|)^-3/2 + u invstd."""
+    cnt = np.asarray(cnt, np.float64)
+    n = cnt.sum()
+    mean, m2 = bn_chan_merge_ref(cnt, mean_k, m2_k)
+    var = m2 / n
+    d = dmean_k.max(1)[:, None]
+    dvar = (dm2_k.sum(1) + (cnt * (4.0 * d * np.abs(mean_k - mean[:, None]) + 4.0 * d * d)).sum(1)) / n
+    low = var + eps - dvar
+    assert (low > 0).all()
+    invstd = (var + eps) ** -0.5
+    return mean, var, (cnt * dmean_k).sum(1) / n + U32 * np.abs(mean) + TINY32, 0.5 * dvar * low ** -1.5 + U32 * invstd, dvar
+
+
+def bn_train_stats_bounds(x, eps):
+    """mgar_bn_train_stats on x (B, C, P): float64 (mean, var, mean bound, invstd bound, var bound)."""
+    B, C, P = x.shape
+    parts = bn_partial_stats_bounds(bn_channel_major(x), bn_chunk(B, C, P), P % 4 == 0)
+    return bn_merge_bounds(*parts, eps)
+
+
+def bn_from_partials_bounds(cnt, mean_k, m2_k, eps, group=256, direct_max=1024):
+    """mgar_bn_stats_from_partials on fp32 partials (C, K): up to 1 024 chunks are merged in double in one step; more are
+    first merged in groups of 256, whose (mean, M2) are rounded to fp32 (u |mean_g|, u M2_g) before the same final merge.
+    2^-40 relative covers the double arithmetic."""
+    cnt, mean_k, m2_k = (np.asarray(a, np.float64) for a in (cnt, mean_k, m2_k))
+    dd = 2.0 ** -40
+    if len(cnt) > direct_max:
+        gc, gm, gq = [], [], []
+        for i in range(0, len(cnt), group):
+            m, q = bn_chan_merge_ref(cnt[i:i + group], mean_k[:, i:i + group], m2_k[:, i:i + group])
+            gc.append(cnt[i:i + group].sum()), gm.append(m), gq.append(q)
+        cnt, mean_k, m2_k = np.array(gc), np.stack(gm, 1), np.stack(gq, 1)
+        dd += U32
+    return bn_merge_bounds(cnt, mean_k, m2_k, dd * np.abs(mean_k) + TINY32, dd * m2_k + TINY32, eps)
