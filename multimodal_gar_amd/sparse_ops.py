@@ -185,6 +185,10 @@ def _note(kernel, rb, c_src, c_dst, n_src, n_dst, rmw):
 
 
 def _gather_gemm(n_out, k, cin, cout, feats, nbr, w, flip):
+    if feats.shape[0] == 0:
+        # no source row (the data gradient of a convolution without an output site): every table entry is -1, and an empty
+        # tensor has no storage to hand to the kernel
+        return torch.zeros((n_out, cout), dtype=torch.float32, device=feats.device)
     out = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
     L.call("mgar_spconv_gather_gemm", n_out, k, cin, cout, L.fptr(feats), L.iptr(nbr), L.fptr(w), int(flip), L.fptr(out),
            L.stream_of(feats))

@@ -72,3 +72,215 @@ def test_voxeliser_matches_the_literal_loop():
     v, c, n = gen.generate(clouds[0])
     w = voxelize_points_loop(clouds[0], vs, rng_xyz, 5, 60)
     assert isinstance(v, np.ndarray) and np.array_equal(v, w[0]) and np.array_equal(c, w[1]) and np.array_equal(n, w[2])
+
+
+# ---- the float64 references of tests/sparse_conv_cases.py, pinned with no kernel involved ---------------------------------------
+# rulebook_ref / gather_gemm_ref / dgrad_ref / dw_ref restate the definition over a dict of sites; here they are held against the
+# dense oracle above, every case is shown to have the property it is named for, and the per-element bound of the device tests
+# is shown to be satisfiable by an fp32 evaluation of the same sums in a shuffled order.
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
+
+import sparse_conv_cases as C  # noqa: E402
+
+
+def _oracle_run(coords, shape, batch, subm, kernel, stride, padding, x, w, cot_of):
+    """dense float64 oracle: out, output sites, shape, d features, d weight (K, Cin, Cout)"""
+    from oracle.cpu_backend import sparse_conv3d_dense
+    kk = C.triple(kernel)
+    K, cin, cout = w.shape
+    f64 = torch.from_numpy(x).double().requires_grad_(True)
+    w64 = torch.from_numpy(w).double().view(*kk, cin, cout).permute(4, 0, 1, 2, 3).contiguous().requires_grad_(True)
+    out, oidx, oshape = sparse_conv3d_dense(f64, torch.from_numpy(coords), list(shape), batch, w64, kernel, stride, padding, subm, {}, None)
+    cot = cot_of(out.shape[0])
+    (out * torch.from_numpy(cot).double()).sum().backward()
+    return (out.detach().numpy(), oidx.numpy(), oshape, f64.grad.numpy(), w64.grad.permute(1, 2, 3, 4, 0).reshape(K, cin, cout).numpy(), cot)
+
+
+def _within(got, ref, S, tol=1e-12):
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    assert (np.abs(got - ref) <= tol * S + 1e-300).all()
+
+
+def _shuffled_fp32(terms, rng):
+    """sequential fp32 sum of `terms` (..., T, C) along T in a random order (cumsum accumulates in its dtype, left to right)"""
+    t = terms[..., rng.permutation(terms.shape[-2]), :].astype(np.float32)
+    return np.cumsum(t, axis=-2, dtype=np.float32)[..., -1, :] if t.shape[-2] else np.zeros(t.shape[:-2] + t.shape[-1:], np.float32)
+
+
+def _fp32_gather(nbr, x, w, rng):
+    K, cin, cout = w.shape
+    if x.shape[0] == 0:                          # no source row: every table entry is -1
+        x = np.zeros((1, cin), np.float32)
+    g = np.where((nbr >= 0)[:, :, None], x[np.maximum(nbr, 0)], np.float32(0))                         # (No, K, Cin)
+    terms = (g[:, :, :, None] * w[None]).reshape(nbr.shape[0], K * cin, cout)                          # fp32 products
+    return _shuffled_fp32(terms, rng)
+
+
+def _fp32_dw(nbr, x, g, rng):
+    out = np.zeros((nbr.shape[1], x.shape[1], g.shape[1]), np.float32)
+    for k in range(nbr.shape[1]):
+        has = nbr[:, k] >= 0
+        terms = x[nbr[has, k]][:, :, None] * g[has][:, None, :]                                        # (P_k, Cin, Cout)
+        out[k] = _shuffled_fp32(np.moveaxis(terms, 0, 1), rng)
+    return out
+
+
+def _assert_bound(got, ref, S, n, m):
+    assert (np.abs(got.astype(np.float64) - ref) <= C.bound(n, m, S)).all()
+
+
+@pytest.mark.parametrize("case,gname,coords,shape,batch,subm,kernel,stride,padding", C.geometry_cases(), ids=C.GEOMETRY_IDS)
+def test_references_equal_the_dense_oracle(case, gname, coords, shape, batch, subm, kernel, stride, padding):
+    if case == "production_keys":               # cannot be densified: the clusters translated into a small grid stand in
+        big, coords = C.production_clusters()
+        big_tables = C.rulebook_ref(big, shape, kernel, stride, padding, subm)
+        shape, batch = C.PRODUCTION_SMALL_SHAPE, 2
+    oidx, oshape, nbr, inv = C.rulebook_ref(coords, shape, kernel, stride, padding, subm)
+    K = nbr.shape[1]
+    cin, cout = 5, 7
+    x, w = C.conv_tensors(case, gname, len(coords), K, cin, cout)
+    want, widx, wshape, dx, dw, cot = _oracle_run(coords, shape, batch, subm, kernel, stride, padding, x, w, lambda n: C.conv_cotangent(n, cout))
+    assert oshape == wshape and np.array_equal(oidx, widx.reshape(-1, 4))
+    ref, S, n = C.gather_gemm_ref(nbr, x, w)
+    _within(ref, want, S)
+    assert np.array_equal(n, (nbr >= 0).sum(1, keepdims=True) * cin * np.ones((1, cout)))
+    dref, dS, dn = C.dgrad_ref(nbr, cot, w, len(coords))
+    _within(dref, dx, dS)
+    wref, wS, wn = C.dw_ref(nbr, x, cot)
+    _within(wref, dw, wS)
+    assert np.array_equal(wn[:, 0, 0], (nbr >= 0).sum(0))
+    # the inverse table names the same pairs as the forward one; the data gradient over it is the same sum
+    fwd = {(o, k, i) for o, k in zip(*np.nonzero(nbr >= 0)) for i in [nbr[o, k]]}
+    bwd = {(inv[i, k], k, i) for i, k in zip(*np.nonzero(inv >= 0))}
+    assert fwd == bwd
+    iref, iS, _ = C.gather_gemm_ref(inv, cot, np.ascontiguousarray(w.transpose(0, 2, 1)))
+    _within(iref, dx, iS)
+    if subm:                                    # its inverse table is the forward one with the offsets mirrored
+        assert np.array_equal(inv, nbr[:, ::-1])
+    # the bound of the device tests can be met: the same sums in fp32, shuffled
+    rng = np.random.default_rng(1)
+    _assert_bound(_fp32_gather(nbr, x, w, rng), ref, S, n, 2)
+    _assert_bound(_fp32_gather(inv, cot, np.ascontiguousarray(w.transpose(0, 2, 1)), rng), dref, dS, dn, 2)
+    _assert_bound(_fp32_dw(nbr, x, cot, rng), wref, wS, wn, 3)
+    if case == "production_keys":
+        # same tables up to the translation (shifts are multiples of the stride; same distances to every face)
+        boidx, boshape, bnbr, binv = big_tables
+        assert np.array_equal(bnbr, nbr) and np.array_equal(binv, inv)
+        st = C.triple(1 if subm else stride)
+        Z, Y, X = C.PRODUCTION_SHAPE
+        shift = np.array([C.PRODUCTION_BATCH - 2, 0, (Y - shape[1]) // st[1], (X - shape[2]) // st[2]])
+        assert (Y - shape[1]) % st[1] == 0 and (X - shape[2]) % st[2] == 0
+        assert np.array_equal(boidx, oidx + shift * (oidx[:, :1] == 1))
+        assert [boshape[0], boshape[1] - shift[2], boshape[2] - shift[3]] == oshape
+        assert C.linear_keys(big, C.PRODUCTION_SHAPE).max() > 2 ** 31
+
+
+def test_every_case_has_the_property_it_is_named_for():
+    inputs = C.geometry_inputs()
+    for n in C.ROWS + (C.PLAN_ROWS,):
+        coords = C.rows_case(n)
+        assert coords.shape == (n, 4) and len(set(map(tuple, coords.tolist()))) == n
+        assert (coords[:, 1:] < C.ROWS_GRID).all() and (coords >= 0).all()
+    nbr, counts, places = C.main_table()
+    assert nbr.shape == (8200, 27) and set(counts) == set(C.COUNT_VALUES) and set(places) == set(C.PLACEMENTS)
+    for name, t in C.builder_tables().items():
+        for k in range(t.shape[1]):
+            rows = t[t[:, k] >= 0, k]
+            assert len(np.unique(rows)) == len(rows), (name, k)                        # injective both ways
+    assert [(nbr[:, k] >= 0).sum() for k in range(27)] == counts
+    for k, pl in enumerate(places):
+        rows = np.flatnonzero(nbr[:, k] >= 0)
+        if pl == "alternate_tiles":
+            assert ((rows // 64) % 2 == 0).all()
+        if pl == "last_block":
+            assert (rows >= 8192).all()
+        if pl == "first" and len(rows):
+            assert rows.max() == len(rows) - 1
+        if pl == "last" and len(rows):
+            assert rows.min() == 8200 - len(rows)
+    for K in C.SMALL_K:
+        assert C.small_table(K).shape == (193, K) and (C.small_table(K)[:, 0] >= 0).all()
+    for p in C.PAIR_ITEM_SIZES:
+        t = C.pair_item_table(p)
+        assert t.shape == (p + 9, 2) and list((t >= 0).sum(0)) == [p, min(p, 65)] and (t[t[:, 1] >= 0, 0] >= 0).all()
+        assert all(len(np.unique(t[t[:, k] >= 0, k])) == (t[:, k] >= 0).sum() for k in (0, 1)) and set(t[:, 1]) <= set(t[:, 0])
+    lb = C.builder_tables()["last_block"]
+    assert not (lb[:1024] >= 0).any() and (lb[1024:, 0] >= 0).all()
+    with pytest.raises(ValueError):
+        C.synthetic_table(8200, 8200, 1, [9], "last_block", 0)
+    # faces: a row with all 27 neighbours and a corner row with 8
+    coords, shape, batch = inputs["faces"]
+    assert len(coords) == 420
+    valid = (C.rulebook_ref(coords, shape, 3, 1, 1, True)[2] >= 0).sum(1)
+    assert valid.max() == 27 and valid.min() == 8 and (valid == 8).sum() == 16
+    # the last cell of sample 0 and the first cell of sample 1 are adjacent linear keys
+    assert np.array_equal(np.sort(C.linear_keys(coords, shape)), np.arange(420))
+    # isolated: the centre tap only
+    coords, shape, batch = inputs["isolated"]
+    nb = C.rulebook_ref(coords, shape, 3, 1, 1, True)[2]
+    assert len(coords) > 20 and np.array_equal(nb[:, 13], np.arange(len(coords))) and (np.delete(nb, 13, 1) == -1).all()
+    # batch_gaps: samples 1 and 3 empty, adjacent linear keys across samples 0 / 2 never pair
+    coords, shape, batch = inputs["batch_gaps"]
+    assert set(coords[:, 0].tolist()) == {0, 2} and batch == 4
+    assert [0, 2, 3, 4] in coords.tolist() and [2, 0, 0, 0] in coords.tolist()
+    for subm, kernel, stride, padding in C.GEOMETRIES.values():
+        oidx, _, nb, inv = C.rulebook_ref(coords, shape, kernel, stride, padding, subm)
+        o, k = np.nonzero(nb >= 0)
+        assert len(o) and (oidx[o, 0] == coords[nb[o, k], 0]).all()
+    # dropped_plane: input rows without any pair; all sites at z = 5: no output site
+    coords, shape, batch = inputs["dropped_plane"]
+    oidx, oshape, nb, inv = C.rulebook_ref(coords, shape, (3, 1, 1), (2, 1, 1), 0, False)
+    assert oshape == [2, 4, 5] and (coords[:, 1] == 5).sum() > 5 and len(oidx) > 5
+    assert ((inv >= 0).sum(1)[coords[:, 1] == 5] == 0).all() and ((inv >= 0).sum(1)[coords[:, 1] < 5] > 0).all()
+    coords, shape, batch = inputs["dropped_plane_only"]
+    oidx, oshape, nb, inv = C.rulebook_ref(coords, shape, (3, 1, 1), (2, 1, 1), 0, False)
+    assert len(coords) > 5 and oidx.shape == (0, 4) and nb.shape == (0, 3) and (inv == -1).all()
+    assert inputs["empty"][0].shape == (0, 4)
+    for subm, kernel, stride, padding in C.GEOMETRIES.values():
+        oidx, _, nb, inv = C.rulebook_ref(inputs["empty"][0], inputs["empty"][1], kernel, stride, padding, subm)
+        assert oidx.shape == (0, 4) and nb.shape[0] == 0 and inv.shape[0] == 0
+    # production_keys: keys above 2^31 at the shipped grid, two clusters
+    coords, shape, batch = inputs["production_keys"]
+    assert len(coords) == 300 and set(coords[:, 0].tolist()) == {0, 31} and C.linear_keys(coords, shape).max() > 2 ** 31
+    # hash: load exactly 0.5, duplicates resolved to the smallest row, bad rows never found
+    hc = C.hash_cases()
+    assert [len(hc["n%d" % n][0]) for n in C.HASH_N] == list(C.HASH_N)
+    coords, q, want = hc["duplicates"]
+    assert want[5] == 5 and want[30] == 5 and want[17] == 2 and want[39] == 0 and want[20] == want[21] == 3
+    coords, q, want = hc["out_of_grid"]
+    assert (want[[0, 7, 13, 21, 30, 39, 4, 25]] == -1).all() and (want >= 0).sum() >= 32
+    for name, (coords, q, want) in hc.items():
+        assert (want[-13:] == -1).all(), name                                           # faces, aliasing keys, b < 0
+    # the restated channel table sorts the plans as the issue lists them
+    assert all(C.register_kernel_takes(*p) == (True, True) for p in C.PLANS_REGISTER_FLOAT4)
+    assert all(C.register_kernel_takes(*p)[0] for p in C.PLANS_REGISTER_SCALAR)
+    assert not any(C.register_kernel_takes(*p)[0] for p in C.PLANS_LDS + C.PLANS_LDS_BIG)
+
+
+@pytest.mark.parametrize("cin,cout", [(16, 16), (33, 40), (1, 1), (128, 128)])
+def test_bound_can_be_met_on_the_channel_plans(cin, cout):
+    """fp32 numpy, products rounded, shuffled order: within gamma(n + 2) S on the 193-row table, K = 27 and K = 1."""
+    coords = C.rows_case(C.PLAN_ROWS)
+    for nbr in (C.rulebook_ref(coords, C.ROWS_GRID, 3, 1, 1, True)[2], C.small_table(1)):
+        K = nbr.shape[1]
+        rng = np.random.default_rng(cin + cout)
+        x, w = C.wide_range(rng, (C.PLAN_ROWS, cin)), C.weights(rng, K, cin, cout)
+        for flip in (0, 1):
+            ref, S, n = C.gather_gemm_ref(nbr, x, w, flip)
+            _assert_bound(_fp32_gather(nbr, x, w[::-1] if flip else w, rng), ref, S, n, 2)
+
+
+def test_bound_can_be_met_on_the_main_table_weight_gradient():
+    nbr, counts, _ = C.main_table()
+    rng = np.random.default_rng(4)
+    x, g = C.wide_range(rng, (C.MAIN_ROWS, 3)), C.wide_range(rng, (C.MAIN_ROWS, 5))
+    ref, S, n = C.dw_ref(nbr, x, g)
+    assert np.array_equal(n[:, 0, 0], counts)
+    _assert_bound(_fp32_dw(nbr, x, g, rng), ref, S, n, 2 + 2)
+    assert (ref[np.array(counts) == 0] == 0).all()
+    pi, po, cnt = C.pair_lists(nbr)
+    assert list(cnt) == counts and len(pi) == sum(counts)
+    at = np.concatenate([[0], np.cumsum(cnt)])
+    for k in range(27):
+        assert (np.diff(po[at[k]:at[k + 1]]) > 0).all() and np.array_equal(nbr[po[at[k]:at[k + 1]], k], pi[at[k]:at[k + 1]])

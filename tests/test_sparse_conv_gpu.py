@@ -234,8 +234,8 @@ def test_device_pair_list_builder_equals_the_torch_definition(subm, kernel, stri
 def test_register_gather_kernel_equals_lds_kernel(cin, cout, flip):
     """spconv_os_kernel (gathered rows straight into the MFMA's A registers, double-buffered W in LDS; round 3) against the
     LDS-staged spconv_gather_gemm_kernel on the same table: same sums in another order.  Ragged last tile, rows without any
-    neighbour, mirrored offsets (the submanifold data gradient); (24, 40) falls outside the register kernel's channel table and
-    must take the LDS kernel either way."""
+    neighbour, mirrored offsets (the submanifold data gradient); (24, 40) runs the register kernel's scalar path
+    (spconv_os_kernel<32, 2> with C_in < 32 and a C_out tail)."""
     from multimodal_gar_amd import _lib as L, sparse_ops
     shape, batch = [10, 36, 40], 2
     idx = sparse_sites(3, batch, tuple(shape), 0.12).cuda()
