@@ -31,7 +31,7 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
-#define MGAR_ABI_VERSION 15     /* bumped on any signature change; mgar_abi_version() returns it */
+#define MGAR_ABI_VERSION 16    /* bumped on any signature change; mgar_abi_version() returns it */
 
 /* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
@@ -584,6 +584,52 @@ int mgar_dafm_attn_bwd(int S, int total_rows, int D, const int *scene_off, const
                        const float *v, const float *de, float sigma, float scale, const float *att,
                        const float *grad_out, float *gmat, float *grad_q, float *grad_k, float *grad_v,
                        void *stream);
+
+/* ===================== per-scene operations on PACKED scene rows (scenes of unequal actor counts) =====================
+ * The rows of all S scenes are stacked; scene s owns rows [scene_off[s], scene_off[s+1]) and the dense (n_s, n_s) block at
+ * de_off[s], exactly as for mgar_dafm_attn_*.  scene_off (S+1) and de_off (S) are int32 DEVICE arrays; total_rows =
+ * scene_off[S] is passed by the host.  Empty scenes are allowed everywhere.  Common to all five entries: a negative size
+ * (or C / D <= 0) returns MGAR_EINVAL, a channel count that is no multiple of 64 MGAR_EUNSUPPORTED, then S == 0 or
+ * total_rows == 0 returns MGAR_OK with nothing launched and nothing written, then a null pointer returns MGAR_EINVAL --
+ * all before any device call.  No float atomics: every sum has a fixed order, so two runs give the same bits.
+ * Alignment: mgar_scene_pair_geometry reads a row of `boxes`, and the two Gram entries read and write the rows of x, grad_x
+ * four floats at a time, so those base pointers must be 16-byte aligned (with D % 64 == 0 every row then is); every other
+ * pointer needs the alignment of its element type only.
+ *
+ * Scene BatchNorm: training-mode BatchNorm1d of every scene by itself (the reference's per-scene self.bn_rgb(R) /
+ * self.bn_lidar(L), model/gat_model.py:1403-1406) over x (total_rows, C), C % 64 == 0.  Per (scene, channel): mean, then
+ * sum (x - mean)^2 in a second pass, biased variance, y = (x - mean) * (invstd * gamma) + beta.  save_mean, save_invstd,
+ * save_var (the biased variance): (S, C) each, fully written.  A scene of one row gets y = beta (invstd and var saved as
+ * 0); an empty scene writes no row.  running_mean / running_var (both or neither; NULL = none) receive one EMA step per
+ * scene with n_s >= 2, in ascending scene order: r = (1 - momentum) r + momentum * stat, with var * n_s / (n_s - 1) for the
+ * variance; num_batches_tracked (one int64 on the device, may be NULL) advances by the number of such scenes. */
+int mgar_scene_bn_fwd(int S, int total_rows, int C, const int *scene_off, const float *x, const float *gamma,
+                      const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                      long long *num_batches_tracked, float *y, float *save_mean, float *save_invstd, float *save_var,
+                      void *stream);
+/* bwd: grad_x (total_rows, C), grad_gamma (C), grad_beta (C) are fully written (rows of one-row scenes with 0).
+ * workspace: 2 * S * C floats of caller-allocated scratch (per-scene partials of grad_gamma and grad_beta, summed over
+ * scenes in ascending order). */
+int mgar_scene_bn_bwd(int S, int total_rows, int C, const int *scene_off, const float *x, const float *grad_y,
+                      const float *gamma, const float *save_mean, const float *save_invstd, float *workspace,
+                      float *grad_x, float *grad_gamma, float *grad_beta, void *stream);
+
+/* The two label-side matrices of every scene, packed like de of mgar_dafm_attn_fwd (any n_s):
+ *   de_ij = (float) sqrt(max(0, |c_i|^2 + |c_j|^2 - 2 c_i . c_j)) evaluated in double, 0 on the diagonal
+ *           (torchmetrics' pairwise_euclidean_distance(zero_diagonal=True), call site model/gat_model.py:1520);
+ *           centres (total_rows, 3);
+ *   dg    = torchvision.ops.generalized_box_iou of each scene's boxes (total_rows, 4) xyxy with themselves (:1519), fp32:
+ *           inter / union - (hull - union) / hull.  boxes == NULL skips it (dg is then not touched and may be NULL). */
+int mgar_scene_pair_geometry(int S, int total_rows, const int *scene_off, const int *de_off, const float *centres,
+                             const float *boxes, float *de, float *dg, void *stream);
+
+/* Gram matrix of every scene: g_s = x_s x_s^T for x (total_rows, D), D % 64 == 0, written packed like de; every entry
+ * is one fused-multiply-add chain over d ascending (g_ij and g_ji are the same bits).  n_s <= MGAR_DAFM_MAX_N, which
+ * these entries cannot check (see mgar_dafm_attn_fwd).  bwd: grad_x_i = sum_j (grad_g_ij + grad_g_ji) x_j, j ascending. */
+int mgar_scene_gram_fwd(int S, int total_rows, int D, const int *scene_off, const int *de_off, const float *x, float *g,
+                        void *stream);
+int mgar_scene_gram_bwd(int S, int total_rows, int D, const int *scene_off, const int *de_off, const float *x,
+                        const float *grad_g, float *grad_x, void *stream);
 
 /* GATv2 edge-softmax + aggregate (torch_geometric.nn.GATv2Conv arithmetic; call site
  * model/gat_model.py:1082-1094).  Edges are given in CSR form grouped by TARGET node:

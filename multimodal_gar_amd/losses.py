@@ -105,3 +105,65 @@ def mgar_losses_uniform(res, social_group_id, action, social_group_activity, n, 
     out["L_total"] = {"L_bce": l_bce, "L_bce2": l_bce2, "L_total": l_bce + out["L_act"] + out["SG_L_act"],
                       "L_act": out["L_act"] + out["SG_L_act"]}[Loss]
     return out
+
+
+_RAGGED_MASKS = {}
+
+
+def _ragged_masks(counts, dev):
+    """Validity masks of a count list, built on the host once per (counts, device): valid (B, n_max) bool, the count of
+    every scene as float (B,)."""
+    key = (tuple(counts), str(dev))
+    hit = _RAGGED_MASKS.get(key)
+    if hit is None:
+        cnt = torch.tensor(counts, device=dev)
+        hit = (torch.arange(max(counts), device=dev)[None, :] < cnt[:, None], cnt.float())
+        if len(_RAGGED_MASKS) < 64:
+            _RAGGED_MASKS[key] = hit
+    return hit
+
+
+def mgar_losses_ragged(res, social_group_id, action, social_group_activity, counts, Loss="L_total", reference_semantics=True):
+    """The batched objective of mgar_losses_uniform for scenes of unequal actor counts (`counts`: host ints, the valid actors
+    are the leading slots): every term is evaluated at n_max = max(counts) for all scenes at once and masked, and each
+    per-scene mean divides by that scene's own element count.  No Python loop over scenes and, with a count list seen
+    before, no host sync.  Equals mgar_losses(..., person_num=counts) term for term (the same objectives as the uniform
+    form: no eigen term, no L_mse)."""
+    assert Loss in ("L_total", "L_act", "L_bce", "L_bce2")
+    counts = [int(c) for c in counts]
+    n = max(counts)
+    dev = res[0].device
+    valid, cnt = _ragged_masks(counts, dev)
+    vf = valid.float()
+    pair_b = valid[:, :, None] & valid[:, None, :]
+    pair = pair_b.float()
+    A_theta = torch.where(pair_b, res[0][:, :n, :n], 0.5)           # padding never reaches a logarithm
+    heads = [torch.where(valid[:, :, None], t[:, :n], 0.5) for t in res[1:15]]
+    pose, intr, sg_pose, sg_intr = heads[0:3], heads[3:7], heads[7:10], heads[10:14]
+    A_hat = TU.get_adjacency_batched(social_group_id.to(dev), n)
+    label = TU.get_label_from_action_batched(action.to(dev), n)
+    sg_label = TU.get_label_from_action_batched(social_group_activity.to(dev), n)
+    pick = (lambda t: t[-1:]) if reference_semantics else (lambda t: t)     # assigned terms: the last scene only
+
+    mask = (1.0 - torch.eye(n, device=dev)) * pair                              # valid off-diagonal pairs
+    mask_sum = cnt * cnt - cnt
+    el = F.binary_cross_entropy(A_theta, A_hat, reduction='none') * pair
+    l_bce = pick(el.flatten(1).sum(1) / (cnt * cnt)).sum()
+    n_group = (A_hat * mask).flatten(1).sum(1)
+    ratio = ((mask_sum - n_group) / (3 * n_group + 1)).view(-1, 1, 1)
+    l_bce2 = pick((ratio * el * mask * A_hat + el * mask * (A_hat == 0).float()).flatten(1).sum(1) / mask_sum).sum()
+
+    def ce(logit, target):                                                      # soft-label CE, mean over a scene's actors
+        return (-(target * F.log_softmax(logit, dim=-1)).sum(-1) * vf).sum(1) / cnt
+
+    def bce(p, t):                                                              # mean over a scene's (actor, class) elements
+        return (F.binary_cross_entropy(p, t, reduction='none') * vf[:, :, None]).flatten(1).sum(1) / (cnt * p.shape[2])
+    l_pose = pick(sum(ce(pose[k], label[k]) for k in range(3))).sum()
+    l_int = sum(bce(intr[k], label[3 + k]) for k in range(4)).sum()
+    sg_l_pose = pick(sum(bce(sg_pose[k], sg_label[k]) for k in range(3))).sum()
+    sg_l_int = sum(bce(sg_intr[k], sg_label[3 + k]) for k in range(4)).sum()
+    out = {"L_bce": l_bce, "L_bce2": l_bce2, "L_pose": l_pose, "L_interaction": l_int, "L_act": l_pose + l_int,
+           "SG_L_pose": sg_l_pose, "SG_L_interaction": sg_l_int, "SG_L_act": sg_l_pose + sg_l_int}
+    out["L_total"] = {"L_bce": l_bce, "L_bce2": l_bce2, "L_total": l_bce + out["L_act"] + out["SG_L_act"],
+                      "L_act": out["L_act"] + out["SG_L_act"]}[Loss]
+    return out

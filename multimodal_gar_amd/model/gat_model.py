@@ -34,6 +34,7 @@ from .. import vision_ops as TO
 from .. import graph_ops as pyg_nn
 from ..metric_ops import pairwise_cosine_similarity, pairwise_euclidean_distance
 from ..dafm_ops import dafm_attention, scene_offsets
+from ..scene_ops import scene_batch_norm, scene_gram, scene_layout, scene_pair_geometry
 from ..pcdet.models import build_network, load_data_to_gpu
 
 
@@ -560,9 +561,12 @@ class GAR_Fusion_Net3(nn.Module):
     def forward(self, RGB_feature, LiDAR_feature, bboxes, bboxes3d, social_group_id, person_id):
         """RGB_feature / LiDAR_feature (B, MAX_NUM_PROPOSAL, 512), bboxes (B, MNP, 4) xyxy,
         bboxes3d (B, MNP, 7) -> 16 zero-padded tensors in the order of reference :1696."""
-        if self._can_batch(RGB_feature, LiDAR_feature, person_id):
-            return self._forward_batched(RGB_feature, LiDAR_feature, bboxes, bboxes3d, person_id)
-        return self.forward_per_scene(RGB_feature, LiDAR_feature, bboxes, bboxes3d, social_group_id, person_id)
+        counts = self._scene_counts(RGB_feature, LiDAR_feature, person_id)
+        if counts is None:
+            return self.forward_per_scene(RGB_feature, LiDAR_feature, bboxes, bboxes3d, social_group_id, person_id)
+        if all(c == counts[0] for c in counts):
+            return self._forward_batched(RGB_feature, LiDAR_feature, bboxes, bboxes3d, person_id, counts[0])
+        return self._forward_ragged(RGB_feature, LiDAR_feature, bboxes, bboxes3d, counts)
 
     def forward_per_scene(self, RGB_feature, LiDAR_feature, bboxes, bboxes3d, social_group_id, person_id):
         cfg = self.cfg
@@ -611,23 +615,46 @@ class GAR_Fusion_Net3(nn.Module):
         return (A_list, *ind_lists, *sg_lists, card_list)
 
     # ------------------------------------------------------------------ batched route
-    def _can_batch(self, RGB_feature, LiDAR_feature, person_id):
+    def _scene_counts(self, RGB_feature, LiDAR_feature, person_id):
+        """Actors per scene (host ints) when the batch can take a batched route -- _forward_batched for equal counts,
+        _forward_ragged otherwise -- and None when it goes scene by scene: another configuration than the shipped one, valid
+        slots that are not the leading columns, a scene of fewer than 2 (BatchNorm1d raises there, and so does the per-scene
+        route) or more than MGAR_DAFM_MAX_N actors, or an empty batch.  The caller can promise the counts and spare the host
+        read: `uniform_actor_count` (one int for every scene) or `actor_counts` (a sequence of host ints, one per scene); where
+        both are set, `uniform_actor_count` is the one that holds."""
+        if RGB_feature is None or LiDAR_feature is None or not self._scene_counts_ok([2]):
+            return None
+        S, MNP = person_id.shape
+        if S == 0:
+            return None
+        n = getattr(self, "uniform_actor_count", None)
+        if n:                                           # caller's promise: skips the host read below
+            return [int(n)] * S
+        counts = getattr(self, "actor_counts", None)
+        if counts is not None:                          # the same promise, one count per scene
+            counts = [int(c) for c in counts]
+            if len(counts) != S:
+                raise ValueError("actor_counts promises %d scenes, the batch has %d" % (len(counts), S))
+        else:
+            # the valid slots are person_id >= 0 and must be the leading columns; one host read for counts and flag together
+            valid = person_id >= 0
+            cnt = valid.sum(dim=1)
+            leading = (valid == (torch.arange(MNP, device=person_id.device)[None, :] < cnt[:, None])).all()
+            host = torch.cat((cnt, leading.view(1).to(cnt.dtype))).tolist()
+            if not host[-1]:
+                return None
+            counts = host[:-1]
+        if not self._scene_counts_ok(counts) or min(RGB_feature.shape[1], LiDAR_feature.shape[1]) < max(counts):
+            return None
+        return counts
+
+    def _scene_counts_ok(self, counts):
+        """Whether scenes of these actor counts can take a batched route under this configuration."""
         cfg = self.cfg
-        if RGB_feature is None or LiDAR_feature is None or cfg.get("DISABLE_BATCHED"):
-            return False
         ok = (cfg.MODALITY == 'Multi' and cfg.FUSION == 'Attention_mat' and cfg.sim == 'cosine' and cfg.FEAT_NORM
               and cfg.get("ind_action_concat") and not cfg.get("sg_feat_org") and not cfg.get("Social_Layer")
-              and not cfg.get("Social_Encoder") and not cfg.get("Action_concat"))
-        if not ok:
-            return False
-        if getattr(self, "uniform_actor_count", None):  # caller's promise: skips the host syncs below
-            return True
-        # equal actor count in every scene: the valid slots are person_id >= 0 in the leading columns
-        valid = person_id >= 0
-        counts = valid.sum(dim=1)
-        n = int(counts[0].item())
-        same = bool((counts == n).all().item()) and bool(valid[:, :n].all().item())
-        return same and n >= 2 and n <= 128 and RGB_feature.shape[1] >= n and LiDAR_feature.shape[1] >= n
+              and not cfg.get("Social_Encoder") and not cfg.get("Action_concat") and not cfg.get("DISABLE_BATCHED"))
+        return bool(ok) and len(counts) > 0 and min(counts) >= 2 and max(counts) <= 128
 
     def _scene_bn(self, bn, x):
         """BatchNorm1d applied to every scene separately (per-scene statistics, like the reference's
@@ -647,9 +674,9 @@ class GAR_Fusion_Net3(nn.Module):
             bn.num_batches_tracked += s
         return y
 
-    def _forward_batched(self, RGB_feature, LiDAR_feature, bboxes, bboxes3d, person_id):
+    def _forward_batched(self, RGB_feature, LiDAR_feature, bboxes, bboxes3d, person_id, n=None):
         S, MNP = person_id.shape
-        n = getattr(self, "uniform_actor_count", None) or int((person_id[0] >= 0).sum().item())
+        n = n or getattr(self, "uniform_actor_count", None) or int((person_id[0] >= 0).sum().item())
         device = RGB_feature.device
         R = self._scene_bn(self.bn_rgb, RGB_feature[:, :n, :])
         L = self._scene_bn(self.bn_lidar, LiDAR_feature[:, :n, :])
@@ -688,18 +715,74 @@ class GAR_Fusion_Net3(nn.Module):
         A_list[:, :n, :n] = A_theta
         return (A_list, *outs, card_list)
 
-    def _heads_stacked(self, prefix, feat, S, n, MNP):
+    def _forward_ragged(self, RGB_feature, LiDAR_feature, bboxes, bboxes3d, counts):
+        """The batched route for scenes of unequal actor counts: the valid rows of the padded inputs, packed."""
+        S, MNP = bboxes.shape[0], bboxes.shape[1]
+        device = RGB_feature.device
+
+        def rows_of(t):                                 # the padded width is each tensor's own
+            return t.reshape(S * t.shape[1], t.shape[2])[scene_layout(counts, t.shape[1], device).row_slot]
+        return self.forward_packed(rows_of(RGB_feature), rows_of(LiDAR_feature), rows_of(bboxes), rows_of(bboxes3d)[:, :3],
+                                   counts, MNP)
+
+    def _packed_bn(self, bn, x, scene_off):
+        if not self.training:
+            return (x - bn.running_mean) / torch.sqrt(bn.running_var + bn.eps) * bn.weight + bn.bias
+        return scene_batch_norm(x, bn.weight, bn.bias, scene_off, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                bn.eps, bn.momentum)
+
+    def forward_packed(self, R, L, bb, ctr, counts, MNP):
+        """R, L (rows, 512), bb (rows, 4) xyxy, ctr (rows, 3): the rows of all scenes stacked, scene s holding counts[s] of
+        them (host ints, each 2..MGAR_DAFM_MAX_N) -> the 16 zero-padded (S, MNP, .) tensors of forward().  Every step is one
+        launch sequence for all scenes; with a count tuple seen before, nothing reads from or writes to the host."""
+        S, device = len(counts), R.device
+        lay = scene_layout(counts, MNP, device)
+        so, do = lay.scene_off, lay.de_off
+        R = self._packed_bn(self.bn_rgb, R, so)
+        L = self._packed_bn(self.bn_lidar, L, so)
+        de, dg = scene_pair_geometry(ctr, bb, so, do, lay.pairs)
+        Rp, Lp = self.AttFusModule1.forward_stacked(R, L, de, so, do)
+        Rp, Lp = self.AttFusModule2.forward_stacked(Rp, Lp, de, so, do)
+        fused = torch.max(Rp, Lp)
+        fn = fused / fused.norm(dim=1, keepdim=True)
+        Dv = scene_gram(fn, so, do, lay.pairs)
+        A_theta = self.D_embed(torch.stack((Dv, dg), dim=-1)).reshape(-1)                        # (sum n_s^2,)
+        if not self.training:
+            A_theta = A_theta.index_fill(0, lay.diag_index, 1.)
+        A_list = torch.zeros(S * MNP * MNP, device=device, dtype=A_theta.dtype).index_put((lay.pair_index,), A_theta)
+        A_list = A_list.view(S, MNP, MNP)
+        # group ids on the padded tensor: padding entries are 0 < 0.5 and can never be picked; diagonal 1 for valid rows only
+        tmp = A_list.detach().reshape(-1).index_fill(0, lay.pair_index[lay.diag_index], 1.).view(S, MNP, MNP)
+        cols = torch.arange(MNP, device=device).expand(S, MNP, MNP)
+        group_id = torch.where(tmp >= 0.5, cols, torch.full_like(cols, MNP)).min(dim=2).values  # (S, MNP)
+        gflat = group_id.reshape(-1)[lay.row_slot] + so.long()[lay.row_scene]
+        sg_features = self._group_max_pool(fused, gflat)
+        res_feature = torch.cat([R, L], dim=-1)
+        outs = []
+        for prefix, feat in (("", res_feature), ("SG_", sg_features)):
+            outs += self._heads_stacked(prefix, feat, S, None, MNP, lay.row_slot)
+        col_max = fused.new_full((S * lay.n_max, fused.shape[1]), float("-inf")).index_copy(0, lay.row_local, fused)
+        col_max = col_max.view(S, lay.n_max, -1).max(dim=1)[0]
+        card_feature = torch.cat((col_max, A_list.sum(dim=(1, 2)).view(S, 1)), dim=1)            # padding adds exact zeros
+        card_list = self.card_net(card_feature)
+        return (A_list, *outs, card_list)
+
+    def _heads_stacked(self, prefix, feat, S, n, MNP, slot=None):
         """The seven heads that share `feat` (Linear -> ReLU -> Dropout -> Linear -> softmax | sigmoid each,
         reference :1160-1173) evaluated together: one GEMM over the stacked first layers, one dropout mask, one
         block-diagonal GEMM for the second layers, one softmax over the three pose heads and one sigmoid over the
         rest -- ~20 launches instead of ~110 (and as many again in the backward), which is what a rank that holds
-        a single clip is made of.  Returns the reference's per-head (S, MNP, k) tensors (views of one buffer)."""
+        a single clip is made of.  Returns the reference's per-head (S, MNP, k) tensors (views of one buffer).
+        feat holds n rows per scene, or, with `slot`, packed rows whose places in (S * MNP) `slot` gives."""
         heads = [getattr(self, prefix + name) for name, _, _ in _HEAD_SPECS]
         if any(len(h) != 5 for h in heads):      # a head with BatchNorm: not stackable
             outs = []
             for h, (_, k, _) in zip(heads, _HEAD_SPECS):
                 o = torch.zeros([S, MNP, k], device=feat.device, dtype=feat.dtype)
-                o[:, :n] = h(feat).view(S, n, k)
+                if slot is None:
+                    o[:, :n] = h(feat).view(S, n, k)
+                else:
+                    o = o.view(S * MNP, k).index_copy(0, slot, h(feat)).view(S, MNP, k)
                 outs.append(o)
             return outs
         ks = [k for _, k, _ in _HEAD_SPECS]
@@ -721,7 +804,10 @@ class GAR_Fusion_Net3(nn.Module):
             parts.append(torch.softmax(logits[:, :k_soft].reshape(-1, n_soft, ks[0]), dim=2).reshape(-1, k_soft))
         parts.append(torch.sigmoid(logits[:, k_soft:]))
         full = torch.zeros([S, MNP, sum(ks)], device=feat.device, dtype=feat.dtype)
-        full[:, :n] = torch.cat(parts, 1).view(S, n, sum(ks))
+        if slot is None:
+            full[:, :n] = torch.cat(parts, 1).view(S, n, sum(ks))
+        else:
+            full = full.view(S * MNP, sum(ks)).index_copy(0, slot, torch.cat(parts, 1)).view(S, MNP, sum(ks))
         outs, col = [], 0
         for k in ks:
             outs.append(full[:, :, col:col + k])

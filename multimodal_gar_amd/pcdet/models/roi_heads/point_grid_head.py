@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from ...ops.pointnet2.pointnet2_stack import pointnet2_modules as pointnet2_stack_modules
-from .voxelrcnn_head import global_grid_points_of_roi
+from .voxelrcnn_head import global_grid_points_of_roi, valid_roi_layout
 
 
 class PointGridRoIHead(nn.Module):
@@ -30,14 +30,20 @@ class PointGridRoIHead(nn.Module):
 
     def forward(self, batch_dict):
         """gt_boxes (B, N, 7), point_coords (P, 4) [b, x, y, z], point_features (P, C)
-        -> pooled_features (B*N, G^3, C_out)."""
+        -> pooled_features (B*N, G^3, C_out).  With roi_counts (host ints, one per sample: the valid boxes are the leading
+        rows of gt_boxes[b]; 0 is allowed) only those are lifted: pooled_features (sum counts, G^3, C_out)."""
         rois = batch_dict['gt_boxes']
         batch_size = batch_dict['batch_size']
         g = self.grid_size
-        grid_xyz, _ = global_grid_points_of_roi(rois, g)                      # (B*N, G^3, 3)
+        roi_counts = batch_dict.get('roi_counts')
+        if roi_counts is None:
+            grid_xyz, _ = global_grid_points_of_roi(rois, g)                  # (B*N, G^3, 3)
+            per_sample = rois.shape[1] * g ** 3
+            new_cnt = torch.full((batch_size,), per_sample, dtype=torch.int32, device=rois.device)
+        else:
+            rows, new_cnt, _ = valid_roi_layout(roi_counts, batch_size, rois.shape[1], g, rois.device)
+            grid_xyz, _ = global_grid_points_of_roi(rois.view(-1, rois.shape[-1])[rows], g)
         new_xyz = grid_xyz.view(-1, 3).contiguous()
-        per_sample = rois.shape[1] * g ** 3
-        new_cnt = torch.full((batch_size,), per_sample, dtype=torch.int32, device=rois.device)
         coords = batch_dict['point_coords']
         xyz = coords[:, 1:4].contiguous()
         xyz_cnt = batch_dict.get('point_batch_cnt')

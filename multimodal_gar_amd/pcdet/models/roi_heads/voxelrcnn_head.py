@@ -30,6 +30,32 @@ def global_grid_points_of_roi(rois, grid_size):
     return glob + rois[:, 0:3].unsqueeze(dim=1), local
 
 
+_ROI_LAYOUT_CACHE = {}
+
+
+def valid_roi_layout(roi_counts, batch_size, boxes_per_sample, grid_size, device):
+    """For `roi_counts` valid boxes per sample (host ints; the valid boxes are the leading rows of gt_boxes[b]):
+    rows (sum counts,) int64 = b * N + i of every valid box in the (B * N) flattened boxes, grid_cnt (B,) int32 =
+    counts[b] * G^3 grid points per sample, grid_batch (sum counts * G^3,) int64 = sample of every grid point.  Built on the
+    host once per (counts, N, G, device)."""
+    counts = tuple(int(c) for c in roi_counts)
+    if len(counts) != batch_size:
+        raise ValueError("roi_counts holds %d counts for a batch of %d samples" % (len(counts), batch_size))
+    key = (counts, int(boxes_per_sample), int(grid_size), str(device))
+    hit = _ROI_LAYOUT_CACHE.get(key)
+    if hit is None:
+        if any(not 0 <= c <= boxes_per_sample for c in counts):
+            raise ValueError("roi_counts %s: every count must lie in 0..%d" % (list(counts), boxes_per_sample))
+        g3 = grid_size ** 3
+        rows = [b * boxes_per_sample + i for b, c in enumerate(counts) for i in range(c)]
+        hit = (torch.tensor(rows, dtype=torch.int64, device=device),
+               torch.tensor([c * g3 for c in counts], dtype=torch.int32, device=device),
+               torch.tensor([b for b, c in enumerate(counts) for _ in range(c * g3)], dtype=torch.int64, device=device))
+        if len(_ROI_LAYOUT_CACHE) < 64:
+            _ROI_LAYOUT_CACHE[key] = hit
+    return hit
+
+
 class VoxelRCNNHead(nn.Module):
     def __init__(self, backbone_channels, model_cfg, point_cloud_range, voxel_size, num_class=1, **kwargs):
         super().__init__()
@@ -68,13 +94,22 @@ class VoxelRCNNHead(nn.Module):
         rois = batch_dict['gt_boxes']
         batch_size = batch_dict['batch_size']
         g = self.pool_cfg.GRID_SIZE
-        grid_xyz, _ = global_grid_points_of_roi(rois, g)
-        grid_xyz = grid_xyz.view(batch_size, -1, 3)
         lo = self.point_cloud_range
         vs = self.voxel_size
-        coords = torch.cat([(grid_xyz[:, :, i:i + 1] - lo[i]) // vs[i] for i in range(3)], dim=-1)   # x, y, z voxel ids
-        batch_idx = torch.arange(batch_size, device=rois.device, dtype=rois.dtype).view(-1, 1, 1).expand(-1, coords.shape[1], 1)
-        grid_cnt = torch.full((batch_size,), coords.shape[1], dtype=torch.int32, device=rois.device)
+        roi_counts = batch_dict.get('roi_counts')
+        if roi_counts is None:
+            grid_xyz, _ = global_grid_points_of_roi(rois, g)
+            grid_xyz = grid_xyz.view(batch_size, -1, 3)
+            coords = torch.cat([(grid_xyz[:, :, i:i + 1] - lo[i]) // vs[i] for i in range(3)], dim=-1)   # x, y, z voxel ids
+            batch_idx = torch.arange(batch_size, device=rois.device, dtype=rois.dtype).view(-1, 1, 1).expand(-1, coords.shape[1], 1)
+            grid_cnt = torch.full((batch_size,), coords.shape[1], dtype=torch.int32, device=rois.device)
+        else:
+            # only the valid boxes (the leading roi_counts[b] of every sample) are lifted: (sum counts, G^3, C)
+            rows, grid_cnt, grid_batch = valid_roi_layout(roi_counts, batch_size, rois.shape[1], g, rois.device)
+            grid_xyz, _ = global_grid_points_of_roi(rois.view(-1, rois.shape[-1])[rows], g)
+            grid_xyz = grid_xyz.view(-1, 3)
+            coords = torch.cat([(grid_xyz[:, i:i + 1] - lo[i]) // vs[i] for i in range(3)], dim=-1)
+            batch_idx = grid_batch.to(rois.dtype).view(-1, 1)
         pooled = []
         for k, src in enumerate(self.pool_cfg.FEATURES_SOURCE):
             stride = batch_dict['multi_scale_3d_strides'][src]

@@ -94,8 +94,10 @@ class SyntheticDataset:
         self.depth_downsample_factor = None
 
 
-def make_batch(seed, n_clips, n_frames, n_actors, n_points, height, width, device):
-    """Synthetic batch on `device`: dict of tensors (see module docstring for the meaning)."""
+def make_batch(seed, n_clips, n_frames, n_actors, n_points, height, width, device, actor_counts=None):
+    """Synthetic batch on `device`: dict of tensors (see module docstring for the meaning).  actor_counts: one count per
+    clip (every frame of a clip has its clip's count), each at most n_actors: the batch is masked beyond the count as a
+    loader pads it -- ids -1, boxes and labels 0 -- and carries the list; None gives the batch as it always was."""
     sc = S.scene_batch(seed, n_clips * n_frames, n_actors, n_points, num_boxes=n_actors + 1, height=height, width=width)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
     lab = S.scene_labels(seed + 3, n_clips * n_frames, n_actors, num_boxes=n_actors + 1)
@@ -103,15 +105,30 @@ def make_batch(seed, n_clips, n_frames, n_actors, n_points, height, width, devic
     boxes2d = np.zeros((n_clips, n_actors + 1, 4), np.float32)
     for b in range(n_clips):
         boxes2d[b, :n_actors] = S.actor_boxes2d(rng, n_actors, height, width)
+    person_id, group_id, action, activity, boxes3d = (sc["person_id"], lab["social_group_id"], lab["action"],
+                                                      lab["social_group_activity"], sc["bboxes3d"])
+    extra = {}
+    if actor_counts is not None:
+        actor_counts = [int(c) for c in actor_counts]
+        if len(actor_counts) != n_clips or not all(0 <= c <= n_actors for c in actor_counts):
+            raise ValueError("actor_counts: one count in 0..%d per clip, got %s" % (n_actors, actor_counts))
+        person_id, group_id, action, activity, boxes3d = (np.array(x) for x in (person_id, group_id, action, activity, boxes3d))
+        for b, c in enumerate(actor_counts):
+            frames = slice(b * n_frames, (b + 1) * n_frames)
+            person_id[frames, c:] = -1; group_id[frames, c:] = -1
+            action[frames, c:] = 0; activity[frames, c:] = 0; boxes3d[frames, c:] = 0
+            boxes2d[b, c:] = 0
+        extra["actor_counts"] = actor_counts
     return {
+        **extra,
         "images": t(S.images(seed + 2, n_clips, n_frames, height, width)),      # (B, T, 3, H, W)
         "bboxes": t(boxes2d),                                                     # (B, A+1, 4) key-frame boxes
         "points": t(sc["points"]),                                                # (B*T, P, 4)
-        "bboxes3d": t(sc["bboxes3d"]),                                            # (B*T, A+1, 7)
-        "person_id": t(sc["person_id"]),                                          # (B*T, A+1)
-        "social_group_id": t(lab["social_group_id"]),                             # (B*T, A+1) int64, -1 padded
-        "action": t(lab["action"]),                                               # (B*T, A+1, 27)
-        "social_group_activity": t(lab["social_group_activity"]),                 # (B*T, A+1, 27)
+        "bboxes3d": t(boxes3d),                                                   # (B*T, A+1, 7)
+        "person_id": t(person_id),                                                # (B*T, A+1)
+        "social_group_id": t(group_id),                                           # (B*T, A+1) int64, -1 padded
+        "action": t(action),                                                      # (B*T, A+1, 27)
+        "social_group_activity": t(activity),                                     # (B*T, A+1, 27)
         "n_clips": n_clips, "n_frames": n_frames, "n_actors": n_actors,
     }
 
@@ -184,21 +201,22 @@ class ClipModel(nn.Module):
                 crops.append(rb.crop_features(clip, [bboxes[i]]))  # (A+1, 832, 5, 5)
         return crops
 
-    def rgb_tokens_from_crops(self, crops):
-        """Trainable tail: non-local block, pooling, embedding, optional GAT -> (B, A, 512)."""
+    def rgb_tokens_from_crops(self, crops, actor_counts=None):
+        """Trainable tail: non-local block, pooling, embedding, optional GAT -> (B, A, 512); with actor_counts (one per
+        clip) the clips' valid actors only, packed: (sum counts, 512)."""
         from .model.gat_model import fully_connected_edges
         rb = self.net.RGB_backbone
-        a = self.n_actors
         toks = []
-        for c in crops:
+        for i, c in enumerate(crops):
+            a = self.n_actors if actor_counts is None else actor_counts[i]
             tok = rb.embed(c[:a])                                # (A, 512)
             if rb.cfg.GAT_module:
                 tok = rb.GAT_module(tok, fully_connected_edges([a], tok.device))
             toks.append(tok)
-        return torch.stack(toks)
+        return torch.stack(toks) if actor_counts is None else torch.cat(toks)
 
-    def rgb_tokens(self, images, bboxes):
-        return self.rgb_tokens_from_crops(self.rgb_crops(images, bboxes))
+    def rgb_tokens(self, images, bboxes, actor_counts=None):
+        return self.rgb_tokens_from_crops(self.rgb_crops(images, bboxes), actor_counts)
 
     # ---- LiDAR: all frames of all clips in one batch ------------------------------------------------
     def trunk_geometry(self, points, stream, whole_chain):
@@ -211,7 +229,9 @@ class ClipModel(nn.Module):
         only_fps1 = {} if whole_chain else dict(levels=1, balls=False, neighbours=False)
         return self.net.LiDAR_backbone.model.backbone_3d.geometry(points, stream, **only_fps1)
 
-    def lidar_tokens(self, points, bboxes3d, geometry=None):
+    def lidar_tokens(self, points, bboxes3d, geometry=None, actor_counts=None):
+        """-> (F, A, 512); with actor_counts (one per clip) only the valid boxes are lifted (roi_counts of the RoI heads) and
+        the tokens come packed: (sum of the frames' counts, 512)."""
         f, p, _ = points.shape
         a = self.n_actors
         lb = self.net.LiDAR_backbone
@@ -225,8 +245,10 @@ class ClipModel(nn.Module):
         else:
             data = voxelize_batch(points, self.dataset)
             data["gt_boxes"] = bboxes3d[:, :a, :].contiguous()
+        if actor_counts is not None:
+            data["roi_counts"] = _frame_counts(actor_counts, f // len(actor_counts))
         tok = lb(data)                                           # (1, F*A, 512)
-        return tok.view(f, a, -1)
+        return tok.view(f, a, -1) if actor_counts is None else tok.view(-1, tok.shape[-1])
 
     def finish_prefetch(self):
         """Pipelined schedule, after the step's BACKWARD (its saved index tensors are the current geometry): join the streams
@@ -247,6 +269,13 @@ class ClipModel(nn.Module):
         if geometry and self._geometry_stream is None:
             self._geometry_stream = torch.cuda.Stream()
 
+    def _counts(self, batch):
+        """The batch's per-clip actor counts, or None when it has none or every clip is full (the uniform path, as ever)."""
+        counts = batch.get("actor_counts")
+        if counts is None or all(int(c) == self.n_actors for c in counts):
+            return None
+        return counts
+
     def forward(self, batch):
         """Picks one of three stream schedules; each joins its side streams into the issuing stream before the fusion net."""
         if not (batch["images"].is_cuda and self.overlap_branches):
@@ -257,9 +286,10 @@ class ClipModel(nn.Module):
 
     def _forward_serial(self, batch):
         """Everything on the current stream, in order: RGB branch, LiDAR branch, fusion net."""
-        rgb = self.rgb_tokens(batch["images"], batch["bboxes"])                   # (B, A, 512)
-        lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"])             # (B*T, A, 512)
-        return self._fuse(batch, rgb, lidar)
+        counts = self._counts(batch)
+        rgb = self.rgb_tokens(batch["images"], batch["bboxes"], counts)            # (B, A, 512)
+        lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"], None, counts)   # (B*T, A, 512)
+        return self._fuse(batch, rgb, lidar, counts)
 
     def _forward_forked(self, batch):
         """Both branches away from the stream the step is issued (and captured) on, which only forks and joins:
@@ -274,6 +304,7 @@ class ClipModel(nn.Module):
         The backward of each branch runs on the stream of its forward.  The measurements behind the issue order, the RGB tail
         on the RGB stream and the 60-cloud limit of the geometry stream: DESIGN.md section 4a."""
         points = batch["points"]
+        counts = self._counts(batch)
         use_geometry_stream = self.route == "pointnet2" and points.shape[0] <= self.geometry_stream_max_clouds
         self._make_streams(lidar=True, geometry=use_geometry_stream)
         main = torch.cuda.current_stream()
@@ -281,14 +312,14 @@ class ClipModel(nn.Module):
         self._rgb_stream.wait_event(inputs_ready)
         with torch.cuda.stream(self._rgb_stream):
             crops = self.rgb_crops(batch["images"], batch["bboxes"])
-            rgb = self.rgb_tokens_from_crops(crops)
+            rgb = self.rgb_tokens_from_crops(crops, counts)
         geometry = None
         if use_geometry_stream:
             self._geometry_stream.wait_event(inputs_ready)
             geometry = self.trunk_geometry(points, self._geometry_stream, whole_chain=True)
         self._lidar_stream.wait_event(inputs_ready)
         with torch.cuda.stream(self._lidar_stream):
-            lidar = self.lidar_tokens(points, batch["bboxes3d"], geometry)
+            lidar = self.lidar_tokens(points, batch["bboxes3d"], geometry, counts)
         if use_geometry_stream:
             main.wait_stream(self._geometry_stream)
         main.wait_stream(self._rgb_stream)
@@ -298,7 +329,7 @@ class ClipModel(nn.Module):
                 c.record_stream(main)
             lidar.record_stream(main)
             rgb.record_stream(main)
-        return self._fuse(batch, rgb, lidar)
+        return self._fuse(batch, rgb, lidar, counts)
 
     def _forward_pipelined(self, batch):
         """Input-side software pipelining (``geometry_prefetch`` and / or ``rgb_prefetch``): the LiDAR branch, the trainable
@@ -314,6 +345,7 @@ class ClipModel(nn.Module):
 
         ``finish_prefetch`` joins what ran for the next batch, after the backward."""
         geometry_prefetch = self.geometry_prefetch and self.route == "pointnet2"
+        counts = self._counts(batch)
         self._make_streams(geometry=geometry_prefetch)
         main = torch.cuda.current_stream()
         inputs_ready = main.record_event()
@@ -334,14 +366,14 @@ class ClipModel(nn.Module):
             self._rgb_stream.wait_event(inputs_ready)
             with torch.cuda.stream(self._rgb_stream):
                 crops = self.rgb_crops(batch["images"], batch["bboxes"])
-        lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"], geometry)   # (B*T, A, 512)
+        lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"], geometry, counts)   # (B*T, A, 512)
         if not self.rgb_prefetch:
             main.wait_stream(self._rgb_stream)
             if not torch.cuda.is_current_stream_capturing():   # inside a graph the pool is private and replays are serial
                 for c in crops:
                     c.record_stream(main)
-        rgb = self.rgb_tokens_from_crops(crops)                                   # (B, A, 512)
-        out = self._fuse(batch, rgb, lidar)
+        rgb = self.rgb_tokens_from_crops(crops, counts)                           # (B, A, 512)
+        out = self._fuse(batch, rgb, lidar, counts)
         if self.rgb_prefetch:
             # the NEXT batch's frozen RGB pass (the caller passes its frames; the benchmark's batches are all the same tensor),
             # issued where the forward ends
@@ -350,7 +382,9 @@ class ClipModel(nn.Module):
                 self._rgb_next = self.rgb_crops(batch.get("next_images", batch["images"]), batch.get("next_bboxes", batch["bboxes"]))
         return out
 
-    def _fuse(self, batch, rgb, lidar):
+    def _fuse(self, batch, rgb, lidar, counts=None):
+        if counts is not None:
+            return self._fuse_ragged(batch, rgb, lidar, counts)
         b, t, a = batch["n_clips"], batch["n_frames"], self.n_actors
         rgb_s = rgb[:, None].expand(b, t, a, rgb.shape[-1]).reshape(b * t, a, -1)   # every frame-scene of a clip
         pad = lambda x: torch.cat([x, x.new_zeros(x.shape[0], 1, x.shape[2])], 1)    # noqa: E731  -> MNP = A + 1
@@ -359,6 +393,54 @@ class ClipModel(nn.Module):
         # configuration (under the bf16 configurations the token producers above are bf16; the tokens are widened here).
         with torch.autocast(device_type=rgb_s.device.type, enabled=False):
             return self.net.GAR_model(pad(rgb_s.float()), pad(lidar.float()), bb2, batch["bboxes3d"], None, batch["person_id"])
+
+    def _fuse_ragged(self, batch, rgb, lidar, counts):
+        """rgb: the clips' tokens packed (sum of the clips' counts, 512); lidar: the frame-scenes' tokens packed.  Every
+        frame-scene of a clip takes its clip's RGB rows and key-frame boxes through a cached index; the fusion net gets
+        packed rows and the frames' counts, so nothing is padded and gathered again."""
+        from .scene_ops import scene_layout
+        t, mnp = batch["n_frames"], self.n_actors + 1
+        frames = _frame_counts(counts, t)
+        dev = lidar.device
+        tok_rows, box_rows = _clip_rows(counts, t, mnp, dev)
+        slot = scene_layout(frames, mnp, dev).row_slot
+        gar = self.net.GAR_model
+        with torch.autocast(device_type=dev.type, enabled=False):
+            R, L = rgb.float()[tok_rows], lidar.float()
+            bb = batch["bboxes"].reshape(-1, 4)[box_rows]
+            b3 = batch["bboxes3d"].reshape(-1, batch["bboxes3d"].shape[-1])[slot]
+            if gar._scene_counts_ok(frames):
+                return gar.forward_packed(R, L, bb, b3[:, :3], frames, mnp)
+            # scene by scene, as the reference loops: the same rows in the zero-padded tensors of its interface
+            s = len(frames)
+            pad = lambda x: x.new_zeros(s * mnp, x.shape[1]).index_copy(0, slot, x).view(s, mnp, -1)    # noqa: E731
+            return gar.forward_per_scene(pad(R), pad(L), pad(bb), batch["bboxes3d"], None, batch["person_id"])
+
+
+_CLIP_ROWS = {}
+
+
+def _frame_counts(actor_counts, n_frames):
+    """Per-clip counts -> one count per frame-scene (every frame of a clip has its clip's count)."""
+    return [int(c) for c in actor_counts for _ in range(n_frames)]
+
+
+def _clip_rows(actor_counts, n_frames, mnp, device):
+    """For every packed frame-scene row: its row in the clips' packed tokens, and its row in the clips' (B * MNP) key-frame
+    boxes.  Built on the host once per (counts, frames, MNP, device)."""
+    key = (tuple(actor_counts), n_frames, mnp, str(device))
+    hit = _CLIP_ROWS.get(key)
+    if hit is None:
+        tok, box, off = [], [], 0
+        for c, a in enumerate(actor_counts):
+            for _ in range(n_frames):
+                tok += range(off, off + a)
+                box += range(c * mnp, c * mnp + a)
+            off += a
+        hit = (torch.tensor(tok, dtype=torch.int64, device=device), torch.tensor(box, dtype=torch.int64, device=device))
+        if len(_CLIP_ROWS) < 64:
+            _CLIP_ROWS[key] = hit
+    return hit
 
 
 def _adopt(stream, current, prefetched):
@@ -421,6 +503,11 @@ def reference_loss(outputs, batch):
     the per-sample terms are summed over the scenes, which is what the reference accumulates at its BATCH_SIZE 1
     (train_func.py:260-269).  As in the reference, the cardinality head is not part of L_total and receives no gradient."""
     from . import losses
+    counts = batch.get("actor_counts")
+    if counts is not None and any(int(c) != batch["n_actors"] for c in counts):
+        return losses.mgar_losses_ragged(outputs, batch["social_group_id"], batch["action"], batch["social_group_activity"],
+                                         _frame_counts(batch["actor_counts"], batch["n_frames"]), Loss="L_total",
+                                         reference_semantics=False)["L_total"]
     return losses.mgar_losses_uniform(outputs, batch["social_group_id"], batch["action"], batch["social_group_activity"],
                                       batch["n_actors"], Loss="L_total", reference_semantics=False)["L_total"]
 
