@@ -31,7 +31,7 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
-#define MGAR_ABI_VERSION 16    /* bumped on any signature change; mgar_abi_version() returns it */
+#define MGAR_ABI_VERSION 17   /* bumped on any signature change; mgar_abi_version() returns it */
 
 /* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
@@ -746,6 +746,19 @@ int mgar_spconv_pairs_dw(int n_items, int K, int Cin, int Cout, const float *in,
                          const int *pair_o, const int *items, const int *item_start, float *partial, float *dw, void *stream);
 int mgar_spconv_dw(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *dout,
                    float *partial, void *stream);
+/* The forward gather-GEMM for bf16 feature rows on the bf16 MFMA (csrc/sparse_conv_bf16.hip; forward only):
+ *   out[o] = bf16( sum_k in[nbr[o, k]] . bf16(w[k']) ),  k' = K-1-k if flip_k else k
+ * in (Ni, Cin) bf16 rows, 16-byte aligned; nbr (No, K) int32, -1 = no neighbour; w (K, Cin, Cout) the fp32 master weight, rounded
+ * to bf16 (nearest even) on every call; out (No, Cout) bf16, fully written.  The sum is accumulated in fp32 over exact bf16 x bf16
+ * products and rounded once on store; a row's bits do not depend on its position in the launch or on No.
+ * Plans: Cin % 16 == 0, 16 <= Cin <= 128, 1 <= Cout <= 128, 1 <= K <= 343 -- any other channel plan returns MGAR_EUNSUPPORTED (the
+ * caller keeps mgar_spconv_gather_gemm), bad sizes / a null pointer with No > 0 / a misaligned `in` MGAR_EINVAL, all before any
+ * device call; No == 0 returns MGAR_OK with nothing launched.  w_packed: caller-allocated, 16-byte aligned scratch of
+ * mgar_spconv_bf16_workspace_bytes(K, Cin, Cout) = K * (Cin / 16) * ceil(Cout / 32) * 1024 bytes (0 for an unsupported plan).
+ * Not `_bf16` twins of the fp32 entry point: another signature, called by name. */
+long long mgar_spconv_bf16_workspace_bytes(int K, int Cin, int Cout);
+int mgar_spconv_bf16_fwd(int No, int K, int Cin, int Cout, const void *in, const int *nbr, const float *w, int flip_k,
+                         void *w_packed, void *out, void *stream);
 
 /* ===================== per-actor point crop ========================
  * points_in_boxes_gpu   pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:98-116; kernel roiaware_pool3d_kernel.cu:313-334

@@ -539,21 +539,32 @@ class _BnActRows(Function):
 
 
 def bn_act_rows(x, bn, relu):
-    """[relu](bn(x)) for a row-major (rows, C) fp32 device tensor and an nn.BatchNorm1d in TRAIN mode (batch statistics, running
-    statistics updated), forward + backward on the row-major kernels; None if the shapes do not qualify (C % 4, C > 1024, eval)."""
-    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and bn.training and x.shape[1] % 4 == 0 and x.shape[1] <= 1024
+    """[relu](bn(x)) for a row-major (rows, C) device tensor and an nn.BatchNorm1d in TRAIN mode (batch statistics, running
+    statistics updated) on the row-major kernels; None if the shapes do not qualify (C % 4, C > 1024, eval).  fp32 rows: forward +
+    backward.  bf16 rows: forward only (None if a gradient is required) -- bf16 in and out, statistics and affine in fp32."""
+    if not (x.is_cuda and x.dim() == 2 and x.dtype in _PAYLOADS and bn.training and x.shape[1] % 4 == 0 and x.shape[1] <= 1024
             and x.shape[0] > 0):
         return None
+    dt = x.dtype
+    if dt != torch.float32 and torch.is_grad_enabled() and (x.requires_grad or (bn.affine and bn.weight.requires_grad)):
+        return None   # the row-major backward (mgar_bn_rows_bwd) takes fp32 payloads only
     x = x.contiguous()
     rows, c = x.shape
     mean = torch.empty((c,), dtype=torch.float32, device=x.device)
     invstd = torch.empty_like(mean)
     ws = torch.empty((max(L.raw("mgar_bn_cl_workspace_floats", 1, rows, c, 0), 1),), dtype=torch.float32, device=x.device)
     track = bn.track_running_stats and bn.running_mean is not None
-    L.call("mgar_bn_cl_train_stats", L.fptr(x), 1, rows, c, 0, float(bn.eps), float(bn.momentum if bn.momentum is not None else 0.1),
-           L.fptr(ws), L.fptr(mean), L.fptr(invstd), L.fptr(bn.running_mean) if track else None, L.fptr(bn.running_var) if track else None,
-           L.dev_ptr(bn.num_batches_tracked, torch.int64) if track and bn.num_batches_tracked is not None else None, L.stream_of(x))
+    L.payload_call("mgar_bn_cl_train_stats", dt, L.pptr(x, dt), 1, rows, c, 0, float(bn.eps),
+                   float(bn.momentum if bn.momentum is not None else 0.1), L.fptr(ws), L.fptr(mean), L.fptr(invstd),
+                   L.fptr(bn.running_mean) if track else None, L.fptr(bn.running_var) if track else None,
+                   L.dev_ptr(bn.num_batches_tracked, torch.int64) if track and bn.num_batches_tracked is not None else None,
+                   L.stream_of(x))
     gamma, beta = _affine(bn, c, x.device)
+    if dt != torch.float32:
+        y = torch.empty_like(x)
+        L.payload_call("mgar_bn_cl_act_fwd", dt, L.pptr(x, dt), 1, rows, c, 0, L.fptr(mean), L.fptr(invstd), L.fptr(gamma), L.fptr(beta),
+                       int(relu), L.pptr(y, dt), c, L.stream_of(x))
+        return y
     return _BnActRows.apply(x, gamma, beta, mean, invstd, relu)
 
 

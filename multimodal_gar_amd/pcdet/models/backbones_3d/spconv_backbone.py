@@ -8,6 +8,7 @@ kernels of csrc/sparse_conv.hip.
 """
 from functools import partial
 
+import torch
 import torch.nn as nn
 
 from ...utils.spconv_utils import spconv
@@ -54,12 +55,25 @@ class VoxelBackBone8x(nn.Module):
         self.num_point_features = 128
         self.backbone_channels = {'x_conv1': 16, 'x_conv2': 32, 'x_conv3': 64, 'x_conv4': 64}
 
+    def _bf16_rows(self, feats):
+        """The trunk after conv_input runs on bf16 rows: under bfloat16 autocast on the device, forward only, switch on."""
+        from .... import sparse_ops
+        if not (sparse_ops.SPCONV_BF16 and feats.is_cuda and feats.dtype == torch.float32 and torch.is_autocast_enabled()
+                and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+            return False
+        return not (torch.is_grad_enabled() and (feats.requires_grad or any(p.requires_grad for p in self.parameters())))
+
     def forward(self, batch_dict):
         """voxel_features (V, C), voxel_coords (V, 4) [b, z, y, x] -> encoded_spconv_tensor + multi-scale features."""
         feats, coords = batch_dict['voxel_features'], batch_dict['voxel_coords']
         x = spconv.SparseConvTensor(features=feats, indices=coords.int(), spatial_shape=self.sparse_shape,
                                     batch_size=batch_dict['batch_size'])
         x = self.conv_input(x)
+        if self._bf16_rows(x.features):
+            # conv_input read fp32 rows (per-voxel means of ABSOLUTE coordinates and intensity: SURVEY.md section 8 keeps
+            # coordinates fp32); its BatchNorm + ReLU output is rounded once, a (V, 16) pass, and every later block runs on bf16
+            # rows (csrc/sparse_conv_bf16.hip, the bf16 row-major BatchNorm).  Indices, rulebooks and hash tables are untouched.
+            x = x.replace_feature(x.features.to(torch.bfloat16))
         x_conv1 = self.conv1(x)
         x_conv2 = self.conv2(x_conv1)
         x_conv3 = self.conv3(x_conv2)

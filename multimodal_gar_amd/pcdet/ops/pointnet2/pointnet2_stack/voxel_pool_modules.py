@@ -120,13 +120,22 @@ class NeighborVoxelSAModuleMSG(nn.Module):
     def _mlp_in_rows(self, k, features):
         """mlps_in[k] = Conv1d(1x1, no bias) + BatchNorm1d on ALL voxels (reference voxel_pool_modules.py:86-88), evaluated on
         the row-major (N, C) features as they are: one GEMM + the row-major BatchNorm kernels (csrc/channels_last.hpp), without
-        the two transposing copies of the (1, C, N) formulation (7.6 + 6 ms per step at config c3).  Device + train mode only."""
+        the two transposing copies of the (1, C, N) formulation (7.6 + 6 ms per step at config c3).  Device + train mode only.
+        bf16 rows (the bf16 trunk, forward only): one bf16 GEMM, then the bf16 row-major BatchNorm -- the (N, C) bf16 result is what
+        mgar_voxel_roi_pool_fwd_bf16 reads."""
         conv, bn = self.mlps_in[k][0], self.mlps_in[k][1]
-        if not (features.is_cuda and features.dtype == torch.float32 and bn.training and conv.bias is None and len(self.mlps_in[k]) == 2):
+        if not (features.is_cuda and bn.training and conv.bias is None and len(self.mlps_in[k]) == 2):
             return None
         from .....bn_ops import bn_act_rows
-        z = _RowsLinear.apply(features.contiguous(), conv.weight.view(conv.out_channels, conv.in_channels))   # (N, C)
-        return bn_act_rows(z, bn, False)
+        w = conv.weight.view(conv.out_channels, conv.in_channels)
+        if features.dtype == torch.bfloat16:
+            if torch.is_grad_enabled() and (features.requires_grad or w.requires_grad):
+                return None
+            return bn_act_rows(features.contiguous() @ w.detach().to(torch.bfloat16).t(), bn, False)
+        if features.dtype != torch.float32:
+            return None
+        z = _RowsLinear.apply(features.contiguous(), w)   # (N, C)
+        return bn_act_rows(z, bn, False) if z.dtype == torch.float32 else None   # under autocast z is bf16: the caller's formulation
 
     def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, new_coords, features, voxel2point_indices):
         """xyz (N, 3) voxel centres, features (N, C_in), new_xyz (M, 3) grid points,

@@ -173,15 +173,15 @@ def _pow2(v):
     return v >= 1 and (v & (v - 1)) == 0
 
 
-def _note(kernel, rb, c_src, c_dst, n_src, n_dst, rmw):
+def _note(kernel, rb, c_src, c_dst, n_src, n_dst, rmw, elem=4.0):
     """Instrumented runs (bench.py): credit a sparse product's algorithmic work -- 2 P C_src C_dst flop over the P (site,
     offset) pairs of the rulebook; bytes = source rows once + destination rows once (twice for the read-modify-write pair
-    kernels) + 8 B of pair indices each."""
+    kernels) at ``elem`` bytes per element + 8 B of pair indices each."""
     if not L.kernel_timing_on():
         return
     p = rb.pair_count()
     L.note_work(kernel, flops=2.0 * p * c_src * c_dst,
-                nbytes=4.0 * (n_src * c_src + (2 if rmw else 1) * n_dst * c_dst) + 8.0 * p)
+                nbytes=elem * (n_src * c_src + (2 if rmw else 1) * n_dst * c_dst) + 8.0 * p)
 
 
 def _gather_gemm(n_out, k, cin, cout, feats, nbr, w, flip):
@@ -214,6 +214,34 @@ PAIRS_FORWARD = False    # forward over pair lists (False: the table-driven, out
 # register-gather kernel (one launch, no read-modify-write; a strided convolution needs its inverse table: one more rulebook
 # launch).  MGAR_SPCONV_DGRAD=pairs|table overrides (A/B in profiles/).
 PAIRS_DGRAD = os.environ.get("MGAR_SPCONV_DGRAD", "table") == "pairs"
+
+
+# bf16 feature rows that need no gradient take the bf16-MFMA forward kernel (csrc/sparse_conv_bf16.hip) and stay bf16.
+# MGAR_SPCONV_BF16=0 (or this flag) restores the widening fp32 path for them (A/B in tests and profiles).
+SPCONV_BF16 = os.environ.get("MGAR_SPCONV_BF16", "1") != "0"
+
+
+def _bf16_forward(feats, w, rb):
+    """out (No, Cout) bf16 = the convolution of bf16 rows on mgar_spconv_bf16_fwd, or None where it does not apply (switch off,
+    not bf16 rows, a gradient is needed, or a channel plan the kernel does not take): the caller runs the fp32 path."""
+    if not (SPCONV_BF16 and feats.dtype == torch.bfloat16):
+        return None
+    if torch.is_grad_enabled() and (feats.requires_grad or w.requires_grad):
+        return None                                    # the gradients exist for fp32 rows only: training stays fp32
+    k, cin, cout = w.shape
+    nbytes = L.raw("mgar_spconv_bf16_workspace_bytes", k, cin, cout)
+    if nbytes == 0:
+        return None
+    n_out = rb.nbr.shape[0]
+    if feats.shape[0] == 0:                            # no source row: every table entry is -1 (see _gather_gemm)
+        return torch.zeros((n_out, cout), dtype=torch.bfloat16, device=feats.device)
+    feats, w = feats.contiguous(), w.detach().contiguous().float()
+    packed = torch.empty((nbytes,), dtype=torch.uint8, device=feats.device)
+    out = torch.empty((n_out, cout), dtype=torch.bfloat16, device=feats.device)
+    L.call("mgar_spconv_bf16_fwd", n_out, k, cin, cout, L.pptr(feats, torch.bfloat16), L.iptr(rb.nbr), L.fptr(w), 0,
+           L.dev_ptr(packed, torch.uint8), L.pptr(out, torch.bfloat16), L.stream_of(feats))
+    _note("spconv_bf16_kernel", rb, cin, cout, feats.shape[0], 0, False, elem=2.0)   # the output write is in the launcher's figure
+    return out
 
 
 class _SparseConv(Function):
@@ -282,5 +310,7 @@ def sparse_conv3d(features, indices, spatial_shape, batch_size, weight, kernel, 
             cache[key] = rb
     cout, cin = weight.shape[0], weight.shape[-1]
     w = weight.permute(1, 2, 3, 4, 0).reshape(rb.K, cin, cout)
-    out = _SparseConv.apply(features, w, rb)
+    out = _bf16_forward(features, w, rb)
+    if out is None:
+        out = _SparseConv.apply(features, w, rb)
     return out, rb.out_indices, rb.out_shape
