@@ -31,7 +31,7 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
-#define MGAR_ABI_VERSION 17   /* bumped on any signature change; mgar_abi_version() returns it */
+#define MGAR_ABI_VERSION 18   /* bumped on any signature change; mgar_abi_version() returns it */
 
 /* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
@@ -714,6 +714,16 @@ int mgar_spconv_output_keys(int n_in, const int *in_coords, const int *geom, lon
  * convolution over its own forward table).  Cin, Cout <= 128 (MGAR_EUNSUPPORTED otherwise). */
 int mgar_spconv_gather_gemm(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *w,
                             int flip_k, float *out, void *stream);
+/* The same product with an eval-mode BatchNorm [+ ReLU] folded into the store (inference: running statistics make the batch
+ * norm a per-channel affine map).  With acc[o][c] the fp32 value mgar_spconv_gather_gemm would have stored (same sum, same order):
+ *   v = fmaf(acc, scale[c], shift[c]);   out = relu ? (v > 0 ? v : (v != v ? v : +0)) : v
+ * -- a NaN passes through the ReLU (torch.relu, the BatchNorm kernels), a negative or -0 pre-activation gives +0.  scale, shift
+ * (Cout) fp32, both required.  Every plan, both kernels (mgar_spconv_set_register_gather) and the timer row of
+ * mgar_spconv_gather_gemm; scale = 1, shift = 0, relu = 0 reproduces its bits.  Refusals as there, all before any device call:
+ * Cin or Cout > 128 MGAR_EUNSUPPORTED, bad sizes / a null pointer with No > 0 MGAR_EINVAL; No == 0 returns MGAR_OK with nothing
+ * launched.  Forward only. */
+int mgar_spconv_gather_gemm_affine(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *w,
+                                   int flip_k, const float *scale, const float *shift, int relu, float *out, void *stream);
 /* Weight gradient: partial (mgar_spconv_dw_chunks(No), K, Cin, Cout) is written; dW = its sum over the first axis
  * (left to the caller: a fixed-order reduction, reproducible). */
 int mgar_spconv_dw_chunks(int No);
@@ -759,6 +769,13 @@ int mgar_spconv_dw(int No, int K, int Cin, int Cout, const float *in, const int 
 long long mgar_spconv_bf16_workspace_bytes(int K, int Cin, int Cout);
 int mgar_spconv_bf16_fwd(int No, int K, int Cin, int Cout, const void *in, const int *nbr, const float *w, int flip_k,
                          void *w_packed, void *out, void *stream);
+/* mgar_spconv_bf16_fwd with the same eval-mode BatchNorm [+ ReLU] epilogue, applied to the fp32 accumulator BEFORE the one
+ * rounding:  out[o][c] = bf16( act( fmaf(acc[o][c], scale[c], shift[c]) ) ),  act as in mgar_spconv_gather_gemm_affine, round to
+ * nearest even on store.  scale, shift (Cout) fp32, both required.  Plans, workspace (mgar_spconv_bf16_workspace_bytes), timer row,
+ * position independence of a row's bits and refusals (unsupported plan MGAR_EUNSUPPORTED; bad sizes / a null pointer with No > 0 /
+ * a misaligned `in` or `w_packed` MGAR_EINVAL; No == 0 MGAR_OK, nothing launched) are those of mgar_spconv_bf16_fwd. */
+int mgar_spconv_bf16_fwd_affine(int No, int K, int Cin, int Cout, const void *in, const int *nbr, const float *w, int flip_k,
+                                const float *scale, const float *shift, int relu, void *w_packed, void *out, void *stream);
 
 /* ===================== per-actor point crop ========================
  * points_in_boxes_gpu   pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:98-116; kernel roiaware_pool3d_kernel.cu:313-334

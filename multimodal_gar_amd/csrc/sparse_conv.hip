@@ -118,10 +118,20 @@ __global__ __launch_bounds__(256) void sp_output_keys_kernel(long long total, in
 constexpr int SC_ROWS = 64;       // output rows per workgroup
 constexpr int SC_MAXC = 128;      // C_in, C_out <= 128
 
+// The eval-mode BatchNorm [+ ReLU] epilogue of the two forward kernels (AFF instantiations): v = fma(acc, scale[c], shift[c]), then
+// relu ? max(v, +0) with a NaN passed through (torch.relu; csrc/bn_act.hip) : v.  A negative or -0 pre-activation gives +0.
+__device__ __forceinline__ float sc_affine(float acc, float scale, float shift, int relu) {
+    const float v = __builtin_fmaf(acc, scale, shift);
+    return relu ? (v > 0.f ? v : (v != v ? v : 0.f)) : v;
+}
+
 // grid ceil(No / 64).  LDS: nbr tile [64][K] ints, A [64][Cin + 1], W [Cin][CoutP] (CoutP = C_out rounded up to 32)
+// AFF: the store applies sc_affine with scale / shift (Cout) -- a lane needs them at its own column cb * 32 + l only.
+template <bool AFF>
 __global__ __launch_bounds__(256) void spconv_gather_gemm_kernel(int No, int K, int Cin, int Cout, const float *__restrict__ in,
                                                                  const int *__restrict__ nbr, const float *__restrict__ w,
-                                                                 int flip_k, float *__restrict__ out) {
+                                                                 int flip_k, const float *__restrict__ scale,
+                                                                 const float *__restrict__ shift, int relu, float *__restrict__ out) {
     extern __shared__ float lds[];
     const int CoutP = (Cout + 31) & ~31, CinP = (Cin + 1) & ~1, ALD = CinP + 1;
     int *nb = reinterpret_cast<int *>(lds);               // [SC_ROWS][K]
@@ -179,10 +189,16 @@ __global__ __launch_bounds__(256) void spconv_gather_gemm_kernel(int No, int K, 
         const int cb = (wave >> 1) + 2 * a;
         const int co = cb * 32 + l;
         if (cb < ncb) {
+            float sc = 1.f, sh = 0.f;
+            if constexpr (AFF) {
+                if (co < Cout) { sc = scale[co]; sh = shift[co]; }
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = sb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;     // D[row][col = l]
-                if (row < nrow && co < Cout) out[(size_t)(o0 + row) * Cout + co] = acc[a][r];
+                float v = acc[a][r];
+                if constexpr (AFF) v = sc_affine(v, sc, sh, relu);
+                if (row < nrow && co < Cout) out[(size_t)(o0 + row) * Cout + co] = v;
             }
         }
     }
@@ -200,9 +216,12 @@ __global__ __launch_bounds__(256) void spconv_gather_gemm_kernel(int No, int K, 
 //     stride along the output channel (conflict-free).
 // Same sums in another order (rows with no neighbour contribute zeros), so results agree with the LDS kernel to fp32 rounding.
 // CINP: C_in rounded up to {4, 16, 32, 64, 128}; NCB: 32-column blocks of the output (C_out <= 32 * NCB).
-template <int CINP, int NCB>
+// AFF: the store applies sc_affine; the lane's NCB scale / shift values (columns 32 a + l) are loaded once, after the last offset,
+// when the gathered-row registers are dead: the main loop and its register budget are those of the plain instantiation.
+template <int CINP, int NCB, bool AFF>
 __global__ __launch_bounds__(256) void spconv_os_kernel(int No, int K, int Cin, int Cout, const float *__restrict__ in,
                                                         const int *__restrict__ nbr, const float *__restrict__ w, int flip_k,
+                                                        const float *__restrict__ scale, const float *__restrict__ shift, int relu,
                                                         float *__restrict__ out) {
     constexpr int CH = CINP / 2;                 // k steps per MFMA half = elements of its row a lane holds
     constexpr int COUTP = NCB * 32;
@@ -286,13 +305,24 @@ __global__ __launch_bounds__(256) void spconv_os_kernel(int No, int K, int Cin, 
         if (k + 1 < K) step(k + 1, 1, areg1, areg0);
     }
     const int obase = blockIdx.x * 128 + wave * 32;
+    float sc[NCB], sh[NCB];
+    if constexpr (AFF) {
+#pragma unroll
+        for (int a = 0; a < NCB; ++a) {
+            const int co = a * 32 + l;
+            sc[a] = co < Cout ? scale[co] : 1.f;
+            sh[a] = co < Cout ? shift[co] : 0.f;
+        }
+    }
 #pragma unroll
     for (int a = 0; a < NCB; ++a) {
         const int co = a * 32 + l;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int orow = obase + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (orow < No && co < Cout) out[(size_t)orow * Cout + co] = acc[a][r];
+            float v = acc[a][r];
+            if constexpr (AFF) v = sc_affine(v, sc[a], sh[a], relu);
+            if (orow < No && co < Cout) out[(size_t)orow * Cout + co] = v;
         }
     }
 }
@@ -787,18 +817,11 @@ MGAR_API int mgar_spconv_output_keys(int n_in, const int *in_coords, const int *
     return check_launch("spconv_output_keys: launch failed");
 }
 
-// out (No, Cout) = sum_k in[nbr[:, k]] . w[k]   with w (K, Cin, Cout) row-major; rows with nbr == -1 contribute nothing.
-// flip_k != 0 reads w[K - 1 - k] (data gradient of a submanifold convolution: its inverse rulebook is the forward one
-// with the offsets mirrored).  out is fully written.  Cin, Cout <= 128.
-MGAR_API int mgar_spconv_gather_gemm(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *w, int flip_k,
-                                     float *out, void *stream) {
-    MGAR_REQUIRE(No >= 0 && K >= 1 && K <= 343 && Cin >= 1 && Cout >= 1, "spconv_gather_gemm: bad sizes");
-    if (Cin > SC_MAXC || Cout > SC_MAXC) {
-        set_error("spconv_gather_gemm: C_in, C_out <= 128");
-        return MGAR_EUNSUPPORTED;
-    }
-    if (No == 0) return MGAR_OK;
-    MGAR_REQUIRE(in && nbr && w && out, "spconv_gather_gemm: null pointer");
+// The two forward entry points below share one launcher.  AFF = false: the plain store (mgar_spconv_gather_gemm, scale / shift
+// unused); AFF = true: the sc_affine store (mgar_spconv_gather_gemm_affine).  Same plans, same kernel choice, same timer row.
+template <bool AFF>
+static int spconv_gather_gemm_launch(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *w, int flip_k,
+                                     const float *scale, const float *shift, int relu, float *out, void *stream) {
     {
         // register-gather kernel (spconv_os_kernel) for the channel counts of VoxelBackBone8x; anything else: the LDS kernel below
         const int cinp = Cin <= 4 ? 4 : (Cin <= 16 ? 16 : (Cin <= 32 ? 32 : (Cin <= 64 ? 64 : 128)));
@@ -809,7 +832,8 @@ MGAR_API int mgar_spconv_gather_gemm(int No, int K, int Cin, int Cout, const flo
 #define SP_OS(CI, NB)                                                                                                        \
         do {                                                                                                                     \
             KtScope kt(KT_SPCONV_GEMM, st, 4.0 * No * ((double)K + Cout) + 4.0 * (double)K * Cin * Cout);                        \
-            hipLaunchKernelGGL((spconv_os_kernel<CI, NB>), grid, dim3(256), 0, st, No, K, Cin, Cout, in, nbr, w, flip_k, out);    \
+            hipLaunchKernelGGL((spconv_os_kernel<CI, NB, AFF>), grid, dim3(256), 0, st, No, K, Cin, Cout, in, nbr, w, flip_k,     \
+                               scale, shift, relu, out);                                                                         \
             return check_launch("spconv_gather_gemm: launch failed");                                                            \
         } while (0)
         if (g_spconv_os && aligned && cinp * ncb * 32 >= 256 && cinp * ncb * 32 * 8 <= 64 * 1024) {
@@ -826,17 +850,47 @@ MGAR_API int mgar_spconv_gather_gemm(int No, int K, int Cin, int Cout, const flo
     const int CoutP = (Cout + 31) & ~31, CinP = (Cin + 1) & ~1;
     const size_t lds = ((size_t)SC_ROWS * K + (size_t)SC_ROWS * (CinP + 1) + (size_t)CinP * CoutP) * sizeof(float);
     MGAR_REQUIRE(lds <= 160 * 1024, "spconv_gather_gemm: tile does not fit LDS");
-    static size_t attr_lds = 0;
+    static size_t attr_lds = 0;                          // one per instantiation of this template = one per kernel
     if (lds > 65536 && lds > attr_lds) {
-        (void)hipFuncSetAttribute((const void *)spconv_gather_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void *)spconv_gather_gemm_kernel<AFF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_lds = lds;
     }
     // table (No, K) read, out written; the gathered input rows and the flops depend on the number of pairs, which the caller
     // credits (mgar_ktimer_add_bytes / _flops)
     KtScope kt(KT_SPCONV_GEMM, (hipStream_t)stream, 4.0 * No * ((double)K + Cout) + 4.0 * (double)K * Cin * Cout);
-    hipLaunchKernelGGL(spconv_gather_gemm_kernel, dim3(ceil_div(No, SC_ROWS)), dim3(256), lds, (hipStream_t)stream, No, K, Cin, Cout, in, nbr,
-                       w, flip_k, out);
+    hipLaunchKernelGGL(spconv_gather_gemm_kernel<AFF>, dim3(ceil_div(No, SC_ROWS)), dim3(256), lds, (hipStream_t)stream, No, K, Cin, Cout,
+                       in, nbr, w, flip_k, scale, shift, relu, out);
     return check_launch("spconv_gather_gemm: launch failed");
+}
+
+// out (No, Cout) = sum_k in[nbr[:, k]] . w[k]   with w (K, Cin, Cout) row-major; rows with nbr == -1 contribute nothing.
+// flip_k != 0 reads w[K - 1 - k] (data gradient of a submanifold convolution: its inverse rulebook is the forward one
+// with the offsets mirrored).  out is fully written.  Cin, Cout <= 128.
+MGAR_API int mgar_spconv_gather_gemm(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *w, int flip_k,
+                                     float *out, void *stream) {
+    MGAR_REQUIRE(No >= 0 && K >= 1 && K <= 343 && Cin >= 1 && Cout >= 1, "spconv_gather_gemm: bad sizes");
+    if (Cin > SC_MAXC || Cout > SC_MAXC) {
+        set_error("spconv_gather_gemm: C_in, C_out <= 128");
+        return MGAR_EUNSUPPORTED;
+    }
+    if (No == 0) return MGAR_OK;
+    MGAR_REQUIRE(in && nbr && w && out, "spconv_gather_gemm: null pointer");
+    return spconv_gather_gemm_launch<false>(No, K, Cin, Cout, in, nbr, w, flip_k, nullptr, nullptr, 0, out, stream);
+}
+
+// mgar_spconv_gather_gemm with an eval-mode BatchNorm [+ ReLU] folded into the store: with acc the fp32 value that entry point
+// would have stored (same sum, same order), out = sc_affine(acc, scale[c], shift[c], relu).  scale, shift (Cout) fp32, both
+// required.  Same plans, kernels (mgar_spconv_set_register_gather) and refusals.
+MGAR_API int mgar_spconv_gather_gemm_affine(int No, int K, int Cin, int Cout, const float *in, const int *nbr, const float *w,
+                                            int flip_k, const float *scale, const float *shift, int relu, float *out, void *stream) {
+    MGAR_REQUIRE(No >= 0 && K >= 1 && K <= 343 && Cin >= 1 && Cout >= 1, "spconv_gather_gemm_affine: bad sizes");
+    if (Cin > SC_MAXC || Cout > SC_MAXC) {
+        set_error("spconv_gather_gemm_affine: C_in, C_out <= 128");
+        return MGAR_EUNSUPPORTED;
+    }
+    if (No == 0) return MGAR_OK;
+    MGAR_REQUIRE(in && nbr && w && scale && shift && out, "spconv_gather_gemm_affine: null pointer");
+    return spconv_gather_gemm_launch<true>(No, K, Cin, Cout, in, nbr, w, flip_k, scale, shift, relu ? 1 : 0, out, stream);
 }
 
 // weight gradient: partial (nchunk, K, Cin, Cout) with nchunk = mgar_spconv_dw_chunks(No); dW = partial.sum(0) (caller).

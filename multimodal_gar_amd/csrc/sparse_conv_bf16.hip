@@ -51,9 +51,13 @@ __global__ __launch_bounds__(256) void spconv_bf16_pack_kernel(const float *__re
 
 // NSP: k-steps the registers are sized for (C_in / 16 rounded up to 1, 2, 4, 8; the steps that exist, ns, are a launch argument);
 // NCB: 32-column blocks of the output.  grid ceil(No / 128).
-template <int NSP, int NCB>
+// AFF: an eval-mode BatchNorm [+ ReLU] in the store -- v = fma(acc, scale[c], shift[c]) in fp32, relu ? max(v, +0) with a NaN
+// passed through : v, and THEN the one rounding to bf16.  The lane's NCB scale / shift values (columns 32 a + l) are loaded once,
+// after the last offset, when the gathered-row registers are dead.
+template <int NSP, int NCB, bool AFF>
 __global__ __launch_bounds__(256) void spconv_bf16_kernel(int No, int K, int Cin, int Cout, const uint16_t *__restrict__ in,
                                                           const int *__restrict__ nbr, const u32x4 *__restrict__ wp,
+                                                          const float *__restrict__ scale, const float *__restrict__ shift, int relu,
                                                           uint16_t *__restrict__ out) {
     constexpr int WPT = (NSP * NCB * 64 + 255) / 256;          // 16-byte vectors of W_k each thread stages
     __shared__ __attribute__((aligned(16))) u32x4 Wl[2][NSP * NCB * 64];
@@ -136,13 +140,27 @@ __global__ __launch_bounds__(256) void spconv_bf16_kernel(int No, int K, int Cin
     }
     // store: register r of a lane is (row = (r & 3) + 8 (r >> 2) + 4 h, column 32 a + l); one rounding, fp32 -> bf16
     const long long obase = (long long)blockIdx.x * SB_ROWS + wave * 32;
+    float sc[NCB], sh[NCB];
+    if constexpr (AFF) {
+#pragma unroll
+        for (int a = 0; a < NCB; ++a) {
+            const int co = a * 32 + l;
+            sc[a] = co < Cout ? scale[co] : 1.f;
+            sh[a] = co < Cout ? shift[co] : 0.f;
+        }
+    }
 #pragma unroll
     for (int a = 0; a < NCB; ++a) {
         const int co = a * 32 + l;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const long long orow = obase + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (orow < No && co < Cout) out[(size_t)orow * Cout + co] = (uint16_t)(pack_bf16x2(acc[a][r], 0.f) & 0xffffu);
+            float v = acc[a][r];
+            if constexpr (AFF) {
+                v = __builtin_fmaf(v, sc[a], sh[a]);
+                if (relu) v = v > 0.f ? v : (v != v ? v : 0.f);
+            }
+            if (orow < No && co < Cout) out[(size_t)orow * Cout + co] = (uint16_t)(pack_bf16x2(v, 0.f) & 0xffffu);
         }
     }
 }
@@ -162,19 +180,11 @@ MGAR_API long long mgar_spconv_bf16_workspace_bytes(int K, int Cin, int Cout) {
     return (long long)K * (Cin / 16) * ceil_div(Cout, 32) * 1024;
 }
 
-// in (Ni, Cin) bf16 rows, nbr (No, K) int32 (-1 = no neighbour), w (K, Cin, Cout) fp32 -> out (No, Cout) bf16, fully written.
-// Cin % 16 == 0, 16 <= Cin <= 128, Cout <= 128, K <= 343: anything else is MGAR_EUNSUPPORTED and the caller keeps the fp32 kernel.
-MGAR_API int mgar_spconv_bf16_fwd(int No, int K, int Cin, int Cout, const void *in, const int *nbr, const float *w, int flip_k,
-                                  void *w_packed, void *out, void *stream) {
-    MGAR_REQUIRE(No >= 0 && K >= 1 && K <= SB_MAXK && Cin >= 1 && Cout >= 1, "spconv_bf16_fwd: bad sizes");
-    if (!sb_plan_ok(K, Cin, Cout)) {
-        set_error("spconv_bf16_fwd: C_in a multiple of 16 in [16, 128], C_out <= 128");
-        return MGAR_EUNSUPPORTED;
-    }
-    if (No == 0) return MGAR_OK;
-    MGAR_REQUIRE(in && nbr && w && w_packed && out, "spconv_bf16_fwd: null pointer");
-    MGAR_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)w_packed & 15) == 0 && ((uintptr_t)out & 1) == 0,
-                 "spconv_bf16_fwd: in and w_packed must be 16-byte aligned");
+// The two forward entry points below share one launcher (arguments already checked).  AFF = false: the plain store; AFF = true:
+// the affine [+ ReLU] store.  Same packing pass, same plans, same timer row.
+template <bool AFF>
+static int spconv_bf16_launch(int No, int K, int Cin, int Cout, const void *in, const int *nbr, const float *w, int flip_k,
+                              const float *scale, const float *shift, int relu, void *w_packed, void *out, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const int ns = Cin / 16, ncb = ceil_div(Cout, 32);
     const long long wtotal = (long long)K * ns * ncb * 512;     // bf16 elements
@@ -191,11 +201,45 @@ MGAR_API int mgar_spconv_bf16_fwd(int No, int K, int Cin, int Cout, const void *
         KtScope kt(KT_SPCONV_BF16, st, 4.0 * No * (double)K + 2.0 * No * (double)Cout + 4.0 * (double)K * Cin * Cout);
 #define SB_CASE(NS, NB)                                                                                                      \
         if (nsp == NS && ncb == NB)                                                                                              \
-            hipLaunchKernelGGL((spconv_bf16_kernel<NS, NB>), grid, dim3(256), 0, st, No, K, Cin, Cout, ip, nbr, wv, op)
+            hipLaunchKernelGGL((spconv_bf16_kernel<NS, NB, AFF>), grid, dim3(256), 0, st, No, K, Cin, Cout, ip, nbr, wv, scale, shift,  \
+                               relu, op)
 #define SB_ROW(NS) SB_CASE(NS, 1); SB_CASE(NS, 2); SB_CASE(NS, 3); SB_CASE(NS, 4)
         SB_ROW(1); SB_ROW(2); SB_ROW(4); SB_ROW(8);
 #undef SB_ROW
 #undef SB_CASE
     }
     return check_launch("spconv_bf16_fwd: launch failed");
+}
+
+// in (Ni, Cin) bf16 rows, nbr (No, K) int32 (-1 = no neighbour), w (K, Cin, Cout) fp32 -> out (No, Cout) bf16, fully written.
+// Cin % 16 == 0, 16 <= Cin <= 128, Cout <= 128, K <= 343: anything else is MGAR_EUNSUPPORTED and the caller keeps the fp32 kernel.
+MGAR_API int mgar_spconv_bf16_fwd(int No, int K, int Cin, int Cout, const void *in, const int *nbr, const float *w, int flip_k,
+                                  void *w_packed, void *out, void *stream) {
+    MGAR_REQUIRE(No >= 0 && K >= 1 && K <= SB_MAXK && Cin >= 1 && Cout >= 1, "spconv_bf16_fwd: bad sizes");
+    if (!sb_plan_ok(K, Cin, Cout)) {
+        set_error("spconv_bf16_fwd: C_in a multiple of 16 in [16, 128], C_out <= 128");
+        return MGAR_EUNSUPPORTED;
+    }
+    if (No == 0) return MGAR_OK;
+    MGAR_REQUIRE(in && nbr && w && w_packed && out, "spconv_bf16_fwd: null pointer");
+    MGAR_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)w_packed & 15) == 0 && ((uintptr_t)out & 1) == 0,
+                 "spconv_bf16_fwd: in and w_packed must be 16-byte aligned");
+    return spconv_bf16_launch<false>(No, K, Cin, Cout, in, nbr, w, flip_k, nullptr, nullptr, 0, w_packed, out, stream);
+}
+
+// mgar_spconv_bf16_fwd with an eval-mode BatchNorm [+ ReLU] folded into the store: out = bf16(act(fma(acc, scale[c], shift[c]))),
+// acc the fp32 accumulator that entry point would have rounded; ONE rounding.  scale, shift (Cout) fp32, both required.  Same
+// plans, workspace and refusals.
+MGAR_API int mgar_spconv_bf16_fwd_affine(int No, int K, int Cin, int Cout, const void *in, const int *nbr, const float *w, int flip_k,
+                                         const float *scale, const float *shift, int relu, void *w_packed, void *out, void *stream) {
+    MGAR_REQUIRE(No >= 0 && K >= 1 && K <= SB_MAXK && Cin >= 1 && Cout >= 1, "spconv_bf16_fwd_affine: bad sizes");
+    if (!sb_plan_ok(K, Cin, Cout)) {
+        set_error("spconv_bf16_fwd_affine: C_in a multiple of 16 in [16, 128], C_out <= 128");
+        return MGAR_EUNSUPPORTED;
+    }
+    if (No == 0) return MGAR_OK;
+    MGAR_REQUIRE(in && nbr && w && scale && shift && w_packed && out, "spconv_bf16_fwd_affine: null pointer");
+    MGAR_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)w_packed & 15) == 0 && ((uintptr_t)out & 1) == 0,
+                 "spconv_bf16_fwd_affine: in and w_packed must be 16-byte aligned");
+    return spconv_bf16_launch<true>(No, K, Cin, Cout, in, nbr, w, flip_k, scale, shift, relu ? 1 : 0, w_packed, out, stream);
 }

@@ -81,6 +81,15 @@ class SparseConvolution(SparseModule):
             feats = feats + self.bias
         return SparseConvTensor(feats, idx, shape, x.batch_size, indice_dict=x.indice_dict)
 
+    def forward_folded(self, x: SparseConvTensor, bn, relu):
+        """[relu](bn(self(x))) for an eval-mode BatchNorm1d, as ONE launch: the batch norm (and this module's bias) as a per-channel
+        scale / shift in the convolution's store (sparse_ops.fold_bn, the *_affine entry points).  Forward only: fold_plan decides."""
+        scale, shift = sparse_ops.fold_bn(bn, self.bias)
+        feats, idx, shape = sparse_ops.sparse_conv3d(x.features, x.indices, x.spatial_shape, x.batch_size, self.weight, self.kernel_size,
+                                                     self.stride, self.padding, self.subm, x.indice_dict, self.indice_key,
+                                                     epilogue=(scale, shift, relu))
+        return SparseConvTensor(feats, idx, shape, x.batch_size, indice_dict=x.indice_dict)
+
 
 class SubMConv3d(SparseConvolution):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True, indice_key=None,
@@ -92,6 +101,34 @@ class SparseConv3d(SparseConvolution):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True, indice_key=None,
                  **kwargs):
         super().__init__(3, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, False, indice_key)
+
+
+def _hooked(module):
+    return bool(module._forward_hooks or module._forward_pre_hooks)
+
+
+def fold_plan(mods, i, feats):
+    """Whether mods[i], a SparseConvolution, runs fused with the BatchNorm1d [+ ReLU] behind it (SparseConvolution.forward_folded):
+    -> (bn, relu, modules consumed: 2 or 3), or None for the unfused path.  Fused when the switch (sparse_ops.SPCONV_FOLD_BN) is on,
+    mods[i + 1] is an nn.BatchNorm1d that is NOT training and has running statistics, the features are fp32 or bf16 rows on the
+    device and no gradient is required: grad mode is off, or neither the features nor a parameter of the two modules requires one.
+    A module of the group that carries a forward hook keeps the group unfused, so the hook still sees its module run.  Reads
+    nothing but attributes: no device work, no synchronisation."""
+    if not sparse_ops.SPCONV_FOLD_BN or i + 1 >= len(mods):
+        return None
+    conv, bn = mods[i], mods[i + 1]
+    if not (isinstance(conv, SparseConvolution) and isinstance(bn, nn.BatchNorm1d)):
+        return None
+    if bn.training or bn.running_mean is None or bn.running_var is None:
+        return None
+    if not (feats.is_cuda and feats.dtype in (torch.float32, torch.bfloat16)):
+        return None
+    if torch.is_grad_enabled() and (feats.requires_grad or any(p.requires_grad for m in (conv, bn) for p in m.parameters())):
+        return None
+    relu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.ReLU)
+    if _hooked(conv) or _hooked(bn) or (relu and _hooked(mods[i + 2])):
+        return None
+    return bn, relu, 3 if relu else 2
 
 
 class SparseSequential(SparseModule):
@@ -119,6 +156,13 @@ class SparseSequential(SparseModule):
         i = 0
         while i < len(mods):
             module = mods[i]
+            if isinstance(module, SparseConvolution) and isinstance(x, SparseConvTensor):
+                plan = fold_plan(mods, i, x.features)
+                if plan is not None:
+                    # inference: conv + BatchNorm1d(eval) [+ ReLU] in one launch, the affine map in the convolution's store
+                    x = module.forward_folded(x, plan[0], plan[1])
+                    i += plan[2]
+                    continue
             if isinstance(module, SparseModule):
                 x = module(x)
             elif isinstance(x, SparseConvTensor):

@@ -244,6 +244,75 @@ def _bf16_forward(feats, w, rb):
     return out
 
 
+# An eval-mode BatchNorm1d [+ ReLU] behind a sparse convolution is folded into the convolution's store (the *_affine entry points
+# of csrc/sparse_conv.hip and csrc/sparse_conv_bf16.hip): inference stays on the kernels through the whole trunk, one launch per
+# block, and bf16 rows are rounded once per block.  MGAR_SPCONV_FOLD_BN=0 (or this flag) restores the separate torch batch norm
+# and ReLU (A/B in tests and profiles).
+SPCONV_FOLD_BN = os.environ.get("MGAR_SPCONV_FOLD_BN", "1") != "0"
+
+
+def fold_bn(bn, conv_bias=None):
+    """An nn.BatchNorm1d with running statistics as the per-channel affine map it is in eval mode -> (scale, shift), fp32 (C,):
+        scale = gamma * rsqrt(running_var + eps),   shift = beta - running_mean * scale  (+ conv_bias * scale)
+    (gamma, beta = 1, 0 without affine), computed in float64 on the tensors' own device and rounded once; no host synchronisation.
+    Cached on the module, keyed on the _version and data_ptr of every tensor read: an in-place update (load_state_dict, an
+    optimiser step) or a replaced tensor recomputes, a second forward launches nothing."""
+    read = [bn.running_mean, bn.running_var]
+    if bn.affine:
+        read += [bn.weight, bn.bias]
+    if conv_bias is not None:
+        read.append(conv_bias)
+    key = (float(bn.eps),) + tuple((t._version, t.data_ptr(), t.device) for t in read)
+    cached = bn.__dict__.get("_mgar_folded")
+    if cached is not None and cached[0] == key:
+        return cached[1], cached[2]
+    with torch.no_grad(), torch.autocast(device_type=bn.running_var.device.type, enabled=False):
+        scale = torch.rsqrt(bn.running_var.detach().double() + float(bn.eps))
+        if bn.affine:
+            scale = scale * bn.weight.detach().double()
+        shift = -bn.running_mean.detach().double() * scale
+        if bn.affine:
+            shift = shift + bn.bias.detach().double()
+        if conv_bias is not None:
+            shift = shift + conv_bias.detach().double() * scale
+        scale, shift = scale.float().contiguous(), shift.float().contiguous()
+    bn.__dict__["_mgar_folded"] = (key, scale, shift)
+    return scale, shift
+
+
+def _affine_forward(feats, w, rb, epilogue):
+    """The convolution with epilogue = (scale, shift, relu) in its store.  bf16 rows on a plan mgar_spconv_bf16_fwd_affine takes
+    (switch on) stay bf16; everything else runs mgar_spconv_gather_gemm_affine on fp32 rows.  Forward only."""
+    scale, shift, relu = epilogue
+    if torch.is_grad_enabled() and (feats.requires_grad or w.requires_grad):
+        raise ValueError("sparse_conv3d: an epilogue is forward only; the features or the weight require a gradient")
+    k, cin, cout = w.shape
+    if tuple(scale.shape) != (cout,) or tuple(shift.shape) != (cout,) or scale.dtype != torch.float32 or shift.dtype != torch.float32:
+        raise ValueError("sparse_conv3d: epilogue scale / shift must be float32 of shape (%d,)" % cout)   # the kernel reads C_out of each
+    n_out = rb.nbr.shape[0]
+    nbytes = L.raw("mgar_spconv_bf16_workspace_bytes", k, cin, cout) if SPCONV_BF16 and feats.dtype == torch.bfloat16 else 0
+    dt = torch.bfloat16 if nbytes else torch.float32
+    scale, shift = scale.contiguous(), shift.contiguous()
+    if feats.shape[0] == 0:
+        # no source row: every table entry is -1 (see _gather_gemm), the accumulator is zero
+        v = torch.zeros((n_out, cout), dtype=torch.float32, device=feats.device) * scale + shift
+        return (torch.relu(v) if relu else v).to(dt)
+    w = w.detach().contiguous().float()
+    out = torch.empty((n_out, cout), dtype=dt, device=feats.device)
+    if nbytes:
+        feats = feats.contiguous()
+        packed = torch.empty((nbytes,), dtype=torch.uint8, device=feats.device)
+        L.call("mgar_spconv_bf16_fwd_affine", n_out, k, cin, cout, L.pptr(feats, dt), L.iptr(rb.nbr), L.fptr(w), 0, L.fptr(scale),
+               L.fptr(shift), int(bool(relu)), L.dev_ptr(packed, torch.uint8), L.pptr(out, dt), L.stream_of(feats))
+        _note("spconv_bf16_kernel", rb, cin, cout, feats.shape[0], 0, False, elem=2.0)
+    else:
+        feats = feats.detach().contiguous().float()
+        L.call("mgar_spconv_gather_gemm_affine", n_out, k, cin, cout, L.fptr(feats), L.iptr(rb.nbr), L.fptr(w), 0, L.fptr(scale),
+               L.fptr(shift), int(bool(relu)), L.fptr(out), L.stream_of(feats))
+        _note("spconv_gemm", rb, cin, cout, feats.shape[0], 0, False)
+    return out
+
+
 class _SparseConv(Function):
     """out (No, Cout) = sum_k feats[nbr[:, k]] @ w[k]  with w (K, Cin, Cout)."""
 
@@ -293,10 +362,12 @@ class _SparseConv(Function):
         return dfeats, dw, None
 
 
-def sparse_conv3d(features, indices, spatial_shape, batch_size, weight, kernel, stride, padding, subm, cache, key):
+def sparse_conv3d(features, indices, spatial_shape, batch_size, weight, kernel, stride, padding, subm, cache, key, epilogue=None):
     """One sparse convolution.  weight: the module's parameter in spconv 2.x layout (Cout, kz, ky, kx, Cin).
     -> (out_features (No, Cout), out_indices (No, 4) int32, out_spatial_shape).  ``cache`` / ``key``: the rulebook of an
-    indice_key is built once per sparse tensor lineage and shared (spconv's indice_dict)."""
+    indice_key is built once per sparse tensor lineage and shared (spconv's indice_dict).
+    ``epilogue`` = (scale (Cout) fp32, shift (Cout) fp32, relu): out = [relu](conv * scale + shift) formed in the kernel's store
+    (fold_bn of an eval-mode BatchNorm; forward only)."""
     rb = cache.get(key) if key is not None else None
     if rb is not None and rb.in_indices.data_ptr() == indices.data_ptr() and rb.in_indices.shape == indices.shape:
         # same lineage: the geometry must be the one the table was built for (spconv asserts the same on a shared indice_key)
@@ -310,6 +381,8 @@ def sparse_conv3d(features, indices, spatial_shape, batch_size, weight, kernel, 
             cache[key] = rb
     cout, cin = weight.shape[0], weight.shape[-1]
     w = weight.permute(1, 2, 3, 4, 0).reshape(rb.K, cin, cout)
+    if epilogue is not None:
+        return _affine_forward(features, w, rb, epilogue), rb.out_indices, rb.out_shape
     out = _bf16_forward(features, w, rb)
     if out is None:
         out = _SparseConv.apply(features, w, rb)
