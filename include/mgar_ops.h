@@ -31,7 +31,7 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
-#define MGAR_ABI_VERSION 18   /* bumped on any signature change; mgar_abi_version() returns it */
+#define MGAR_ABI_VERSION 19   /* bumped on any signature change; mgar_abi_version() returns it */
 
 /* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
@@ -685,6 +685,25 @@ int mgar_voxel_roi_pool_bwd(int M, int nsample, int C, const float *xyz, const f
                             const double *moments, int train_stats, const float *dpooled, const float *pooled,
                             const unsigned char *arg, float *workspace, float *dfeats, int ld_f, float *dgamma,
                             float *dbeta, float *dw_pos, void *stream);
+/* Inference: the same pooling with mlps_out behind it in ONE kernel, every BatchNorm an affine map (running statistics).  feats
+ * (N, ld_f) is mlps_in's output with its BatchNorm folded (one GEMM with bias); per query m, channel c < C, output j < Co:
+ *   r = xyz[idx[m,s]] - new_xyz[m];  p = w_pos[c] . r  (both as mgar_voxel_roi_pool_fwd forms them);
+ *   v = f + fmaf(p, pos_scale[c], pos_shift[c])            f = feats[idx[m,s]][c] widened to fp32
+ *   pooled_c = relu(max_s v)                               an empty neighbourhood (idx[m,0] < 0): f = 0, r = 0, v = pos_shift[c]
+ *   z = sum_c w_out[j*C + c] * pooled_c                    fp32, an fmaf chain over ascending c
+ *   o = fmaf(z, out_scale[j], out_shift[j]);   out[m*ld_out + j] = relu ? (o > 0 ? o : (o != o ? o : +0)) : o
+ * A NaN is sticky in the running max and passes both ReLUs (torch.max / torch.relu); mgar_voxel_roi_pool_fwd drops a NaN in its
+ * `>` / fmaxf and is unchanged.  out is ROW-major (M, ld_out): a column slice of a wider buffer is written in place, columns
+ * j >= Co of a row are not touched.  No arg-max, no atomics, no cross-row state: a row's bits depend on its idx row, the rows it
+ * names and the parameters only -- not on M, its position or its workgroup neighbours.  w_pos (C, 3), w_out (Co, C), the four
+ * vectors fp32 and required.  1 <= C, Co <= 32 (above: MGAR_EUNSUPPORTED), 1 <= nsample <= 255, ld_f >= C, ld_out >= Co; a bad
+ * size or a null pointer with M > 0 is MGAR_EINVAL; M == 0 returns MGAR_OK with nothing launched; every refusal precedes any
+ * device call.  Forward only.  mgar_voxel_roi_pool_eval_bf16_fwd reads bf16 feats and rounds out once, to nearest even; it is called by name, not as a
+ * `_bf16` payload twin of the table at the end of this header. */
+int mgar_voxel_roi_pool_eval_fwd(int M, int nsample, int C, int Co, const float *xyz, const float *new_xyz,
+                                 const float *feats, int ld_f, const int *idx, const float *w_pos, const float *pos_scale,
+                                 const float *pos_shift, const float *w_out, const float *out_scale, const float *out_shift,
+                                 int relu, float *out, int ld_out, void *stream);
 
 /* ============ sparse 3-D convolution: trunk of Voxel R-CNN ====================
  * Replaces the third-party spconv calls of pcdet/models/backbones_3d/spconv_backbone.py:69-170 (SubMConv3d /
@@ -913,6 +932,12 @@ int mgar_stem_conv3d_fwd_bf16(const void *x, int N, int T, int H, int W, const f
 int mgar_voxel_roi_pool_fwd_bf16(int M, int nsample, int C, const float *xyz, const float *new_xyz, const void *feats,
                                  int ld_f, const int *idx, const float *w_pos, const float *mean, const float *invstd,
                                  const float *gamma, const float *beta, void *pooled, unsigned char *arg, void *stream);
+/* feats, out (every parameter vector fp32) */
+int mgar_voxel_roi_pool_eval_bf16_fwd(int M, int nsample, int C, int Co, const float *xyz, const float *new_xyz,
+                                      const void *feats, int ld_f, const int *idx, const float *w_pos,
+                                      const float *pos_scale, const float *pos_shift, const float *w_out,
+                                      const float *out_scale, const float *out_shift, int relu, void *out, int ld_out,
+                                      void *stream);
 
 #ifdef __cplusplus
 }

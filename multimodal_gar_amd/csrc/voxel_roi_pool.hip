@@ -20,6 +20,9 @@
 //   * backward: only the arg-max neighbour of each (query, channel) receives gradient, and the BatchNorm backward of the
 //     position branch needs, besides the moments, just five per-channel sums over those M*C entries -- the weight
 //     gradient is assembled in closed form (see vrp_bwd_finalize_kernel).
+//   * inference (`vrp_eval_kernel`): with running statistics every BatchNorm is an affine map, so the same gather and max run
+//     with mlps_out (Conv1d + BatchNorm1d [+ ReLU], :119-126) behind them in the kernel and the (M, C_out) rows go straight into
+//     the caller's row-major buffer -- no arg-max, no transpose, a NaN propagates as in torch.max / torch.relu.
 // Empty neighbourhoods (voxel_query wrote idx[m][0] = -1): features and relative coordinates are zero, as the reference
 // zeroes them (voxel_pool_modules.py:101,106); they count in the statistics.
 #include "common.hpp"
@@ -155,6 +158,75 @@ __global__ __launch_bounds__(VP_THREADS) void vrp_fwd_kernel(int M, int nsample,
             Payload<T>::st(pooled + (size_t)ch * M + m0 + q, tile[q][ch]);
             arg[(size_t)ch * M + m0 + q] = targ[q][ch];
         }
+    }
+}
+
+// ---- inference forward: pooling + mlps_out, every BatchNorm an affine map ----------------------------------------------
+// grid ceil(M / VP_Q).  Phase 1 is vrp_fwd_kernel's gather (a half-wave per query, lanes along the C channels) with the
+// position BatchNorm as one fmaf and a NaN-carrying max; pooled rows go to LDS (32 consecutive floats per half-wave: no bank
+// conflict).  Phase 2: lane j of the half-wave holds row j of w_out in registers and reads the query's pooled row as
+// broadcast 16-byte LDS reads -- an fmaf chain over ascending c, then the affine [+ ReLU] store of the *_affine sparse-conv
+// entries, Co contiguous elements per half-wave into the row-major (M, ld_out) result.  No arg-max, no transpose.
+__device__ __forceinline__ float relu_nan(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
+
+template <typename T>
+__global__ __launch_bounds__(VP_THREADS) void vrp_eval_kernel(int M, int nsample, int C, int Co, const float *__restrict__ xyz,
+                                                              const float *__restrict__ new_xyz, const T *__restrict__ feats,
+                                                              int ld_f, const int *__restrict__ idx,
+                                                              const float *__restrict__ w_pos, const float *__restrict__ pos_scale,
+                                                              const float *__restrict__ pos_shift, const float *__restrict__ w_out,
+                                                              const float *__restrict__ out_scale,
+                                                              const float *__restrict__ out_shift, int relu, T *__restrict__ out,
+                                                              int ld_out) {
+    __shared__ float4 tile[VP_Q][VP_MAXC / 4];
+    const int c = threadIdx.x & 31, hw = threadIdx.x >> 5;
+    const bool live = c < C;
+    const float w0 = live ? w_pos[c * 3 + 0] : 0.f, w1 = live ? w_pos[c * 3 + 1] : 0.f, w2 = live ? w_pos[c * 3 + 2] : 0.f;
+    const float ps = live ? pos_scale[c] : 0.f, pb = live ? pos_shift[c] : 0.f;
+    const int m0 = blockIdx.x * VP_Q;
+    const int nq = min(VP_Q, M - m0);
+    for (int q = hw; q < nq; q += VP_THREADS / 32) {
+        const int m = m0 + q;
+        const int *id = idx + (size_t)m * nsample;
+        const float qx = new_xyz[(size_t)m * 3], qy = new_xyz[(size_t)m * 3 + 1], qz = new_xyz[(size_t)m * 3 + 2];
+        float best;
+        if (id[0] < 0) {
+            best = pb;                              // every column of an empty neighbourhood: 0 + fmaf(0, ps, pb)
+        } else {
+            best = -__builtin_inff();
+#pragma unroll 4
+            for (int s = 0; s < nsample; ++s) {
+                const int j = id[s];
+                const float rx = xyz[(size_t)j * 3] - qx, ry = xyz[(size_t)j * 3 + 1] - qy, rz = xyz[(size_t)j * 3 + 2] - qz;
+                const float p = w0 * rx + w1 * ry + w2 * rz;
+                const float f = live ? Payload<T>::ld(feats + (size_t)j * ld_f + c) : 0.f;
+                const float v = f + __builtin_fmaf(p, ps, pb);
+                if (v > best || v != v) best = v;   // a NaN enters and stays: nothing compares greater than it
+            }
+        }
+        reinterpret_cast<float *>(tile[q])[c] = live ? relu_nan(best) : 0.f;   // lanes beyond C: exact zeros for the chain below
+    }
+    __syncthreads();
+    const int j = c;
+    const bool lj = j < Co;
+    float w[VP_MAXC];
+#pragma unroll
+    for (int k = 0; k < VP_MAXC; ++k) w[k] = (lj && k < C) ? w_out[j * C + k] : 0.f;
+    const float os = lj ? out_scale[j] : 0.f, ob = lj ? out_shift[j] : 0.f;
+    for (int q = hw; q < nq; q += VP_THREADS / 32) {
+        float z = 0.f;
+#pragma unroll
+        for (int g = 0; g < VP_MAXC / 4; ++g) {
+            if (g * 4 < C) {                        // workgroup-uniform
+                const float4 t = tile[q][g];
+                z = __builtin_fmaf(w[g * 4 + 0], t.x, z);
+                z = __builtin_fmaf(w[g * 4 + 1], t.y, z);
+                z = __builtin_fmaf(w[g * 4 + 2], t.z, z);
+                z = __builtin_fmaf(w[g * 4 + 3], t.w, z);
+            }
+        }
+        const float o = __builtin_fmaf(z, os, ob);
+        if (lj) Payload<T>::st(out + (size_t)(m0 + q) * ld_out + j, relu ? relu_nan(o) : o);
     }
 }
 
@@ -317,6 +389,45 @@ MGAR_API int mgar_voxel_roi_pool_fwd_bf16(int M, int nsample, int C, const float
                                           const float *gamma, const float *beta, void *pooled, unsigned char *arg, void *stream) {
     return vrp_fwd_impl<bf16_t>(M, nsample, C, xyz, new_xyz, (const bf16_t *)feats, ld_f, idx, w_pos, mean, invstd, gamma, beta,
                                 (bf16_t *)pooled, arg, stream);
+}
+
+template <typename T>
+static int vrp_eval_impl(int M, int nsample, int C, int Co, const float *xyz, const float *new_xyz, const T *feats, int ld_f,
+                         const int *idx, const float *w_pos, const float *pos_scale, const float *pos_shift, const float *w_out,
+                         const float *out_scale, const float *out_shift, int relu, T *out, int ld_out, void *stream) {
+    MGAR_REQUIRE(M >= 0 && nsample >= 1 && nsample <= 255 && C >= 1 && Co >= 1,
+                 "voxel_roi_pool_eval_fwd: bad sizes (M >= 0, 1 <= nsample <= 255, C, Co >= 1)");
+    if (C > VP_MAXC || Co > VP_MAXC) {
+        set_error("voxel_roi_pool_eval_fwd: C, Co <= 32");
+        return MGAR_EUNSUPPORTED;
+    }
+    MGAR_REQUIRE(ld_f >= C && ld_out >= Co, "voxel_roi_pool_eval_fwd: bad sizes (ld_f >= C, ld_out >= Co)");
+    if (M == 0) return MGAR_OK;
+    MGAR_REQUIRE(xyz && new_xyz && feats && idx && w_pos && pos_scale && pos_shift && w_out && out_scale && out_shift && out,
+                 "voxel_roi_pool_eval_fwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    // minimum traffic: the index tensor, the queries, the (M, Co) result (the voxel rows are cache-resident gathers)
+    KtScope kt(KT_VOXEL_ROI_POOL_EVAL, st, (double)M * (4.0 * nsample + 12.0 + Co * (double)sizeof(T)),
+               2.0 * M * C * (4.0 * nsample + Co));
+    hipLaunchKernelGGL(vrp_eval_kernel<T>, dim3(vrp_blocks(M)), dim3(VP_THREADS), 0, st, M, nsample, C, Co, xyz, new_xyz, feats, ld_f,
+                       idx, w_pos, pos_scale, pos_shift, w_out, out_scale, out_shift, relu, out, ld_out);
+    return check_launch("voxel_roi_pool_eval_fwd: launch failed");
+}
+
+MGAR_API int mgar_voxel_roi_pool_eval_fwd(int M, int nsample, int C, int Co, const float *xyz, const float *new_xyz,
+                                          const float *feats, int ld_f, const int *idx, const float *w_pos, const float *pos_scale,
+                                          const float *pos_shift, const float *w_out, const float *out_scale,
+                                          const float *out_shift, int relu, float *out, int ld_out, void *stream) {
+    return vrp_eval_impl<float>(M, nsample, C, Co, xyz, new_xyz, feats, ld_f, idx, w_pos, pos_scale, pos_shift, w_out, out_scale,
+                                out_shift, relu, out, ld_out, stream);
+}
+MGAR_API int mgar_voxel_roi_pool_eval_bf16_fwd(int M, int nsample, int C, int Co, const float *xyz, const float *new_xyz,
+                                               const void *feats, int ld_f, const int *idx, const float *w_pos,
+                                               const float *pos_scale, const float *pos_shift, const float *w_out,
+                                               const float *out_scale, const float *out_shift, int relu, void *out, int ld_out,
+                                               void *stream) {
+    return vrp_eval_impl<bf16_t>(M, nsample, C, Co, xyz, new_xyz, (const bf16_t *)feats, ld_f, idx, w_pos, pos_scale, pos_shift, w_out,
+                                 out_scale, out_shift, relu, (bf16_t *)out, ld_out, stream);
 }
 
 MGAR_API int mgar_voxel_roi_pool_bwd(int M, int nsample, int C, const float *xyz, const float *new_xyz, const int *idx,

@@ -110,20 +110,36 @@ class VoxelRCNNHead(nn.Module):
             grid_xyz = grid_xyz.view(-1, 3)
             coords = torch.cat([(grid_xyz[:, i:i + 1] - lo[i]) // vs[i] for i in range(3)], dim=-1)
             batch_idx = grid_batch.to(rois.dtype).view(-1, 1)
+        # inference: when every scale of every source runs on the eval route (eval_fuse_plan), the layers write their columns of
+        # ONE (M, C_total) buffer and nothing is concatenated
+        sources = [batch_dict['multi_scale_3d_features'][src] for src in self.pool_cfg.FEATURES_SOURCE]
+        plan = voxelpool_stack_modules.eval_fuse_plan
+        widths = [sum(m[-1] for m in self.pool_cfg.POOL_LAYERS[src].MLPS) for src in self.pool_cfg.FEATURES_SOURCE]
+        shared = None
+        if len({sp.features.dtype for sp in sources}) == 1 and all(
+                plan(layer, s, sp.features, grid_xyz) is not None
+                for layer, sp in zip(self.roi_grid_pool_layers, sources) for s in range(len(layer.groupers))):
+            shared = torch.empty((grid_xyz.numel() // 3, sum(widths)), dtype=sources[0].features.dtype, device=rois.device)
         pooled = []
+        col = 0
         for k, src in enumerate(self.pool_cfg.FEATURES_SOURCE):
             stride = batch_dict['multi_scale_3d_strides'][src]
-            sp = batch_dict['multi_scale_3d_features'][src]
+            sp = sources[k]
             centres = common_utils.get_voxel_centers(sp.indices[:, 1:4], downsample_times=stride, voxel_size=vs,
                                                      point_cloud_range=lo)
             cnt = torch.bincount(sp.indices[:, 0].long(), minlength=batch_size).int()
             v2p = common_utils.generate_voxel2pinds(sp)
             cur = torch.cat([batch_idx, coords // stride], dim=-1).int()                               # [b, x, y, z]
+            into = {} if shared is None else {'out': shared[:, col:col + widths[k]]}
             feat = self.roi_grid_pool_layers[k](xyz=centres.contiguous(), xyz_batch_cnt=cnt,
                                                 new_xyz=grid_xyz.contiguous().view(-1, 3), new_xyz_batch_cnt=grid_cnt,
                                                 new_coords=cur.contiguous().view(-1, 4), features=sp.features.contiguous(),
-                                                voxel2point_indices=v2p)
-            pooled.append(feat.view(-1, g ** 3, feat.shape[-1]))
+                                                voxel2point_indices=v2p, **into)
+            col += widths[k]
+            if shared is None:
+                pooled.append(feat.view(-1, g ** 3, feat.shape[-1]))
+        if shared is not None:
+            return shared.view(-1, g ** 3, shared.shape[1])
         return torch.cat(pooled, dim=-1)
 
     def forward(self, batch_dict):

@@ -238,6 +238,37 @@ def voxel_roi_pool_fwd(M, nsample, C, xyz, new_xyz, feats, idx_raw, w_pos, mean,
     return 1
 
 
+def _rows_ptr(t, dtype, what):
+    """(pointer, leading dimension) of device rows (n, c) whose elements are consecutive inside a row: a contiguous tensor or a
+    column slice of one."""
+    if not (t.is_cuda and t.dim() == 2 and t.dtype == dtype and (t.shape[1] == 1 or t.stride(1) == 1)):
+        raise L.MgarError("%s: expected 2-D %s device rows with unit column stride" % (what, dtype))
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    if ld < t.shape[1]:
+        raise L.MgarError("%s: rows overlap (row stride %d < %d columns)" % (what, ld, t.shape[1]))
+    return t.data_ptr(), ld
+
+
+def voxel_roi_pool_eval_fwd(M, nsample, C, Co, xyz, new_xyz, feats, idx_raw, w_pos, pos_scale, pos_shift, w_out, out_scale,
+                            out_shift, relu, out):
+    """Inference: pooling + mlps_out of one scale in one kernel (mgar_voxel_roi_pool_eval_fwd, for bf16 rows
+    mgar_voxel_roi_pool_eval_bf16_fwd -- called by name: the entry is no `_bf16` payload twin, see include/mgar_ops.h).  feats (N, >= C) and
+    out (M, Co) rows of the payload dtype, each contiguous or a column slice of a wider buffer: columns beyond Co of that
+    buffer are not written."""
+    import torch
+    dt = feats.dtype
+    if dt not in (torch.float32, torch.bfloat16):
+        raise L.MgarError("voxel_roi_pool_eval_fwd: unsupported payload dtype %s" % dt)
+    fp, ld_f = _rows_ptr(feats, dt, "voxel_roi_pool_eval_fwd: feats")
+    op, ld_out = _rows_ptr(out, dt, "voxel_roi_pool_eval_fwd: out")
+    if feats.shape[1] < C or tuple(out.shape) != (M, Co):
+        raise L.MgarError("voxel_roi_pool_eval_fwd: feats needs >= %d columns, out the shape (%d, %d)" % (C, M, Co))
+    L.call("mgar_voxel_roi_pool_eval_fwd" if dt == torch.float32 else "mgar_voxel_roi_pool_eval_bf16_fwd", M, nsample, C, Co, L.fptr(xyz), L.fptr(new_xyz), fp, ld_f, L.iptr(idx_raw),
+                   L.fptr(w_pos), L.fptr(pos_scale), L.fptr(pos_shift), L.fptr(w_out), L.fptr(out_scale), L.fptr(out_shift),
+                   int(bool(relu)), op, ld_out, L.stream_of(xyz))
+    return 1
+
+
 def voxel_roi_pool_bwd(M, nsample, C, xyz, new_xyz, idx_raw, w_pos, mean, invstd, gamma, moments, train_stats, dpooled, pooled, arg,
                        dfeats, dgamma, dbeta, dw_pos):
     import torch

@@ -4,6 +4,7 @@ Mirror of the reference's pcdet/ops/pointnet2/pointnet2_stack/voxel_pool_modules
 (NeighborVoxelSAModuleMSG): same constructor keywords and sub-module names (groupers,
 mlps_in, mlps_pos, mlps_out).
 """
+import os
 from typing import List
 
 import torch
@@ -14,7 +15,7 @@ from torch.autograd.function import once_differentiable
 
 from . import pointnet2_stack_cuda as pointnet2
 from . import voxel_query_utils
-from .....nn_utils import PointwiseSequential
+from .....nn_utils import PointwiseSequential, _is_pointwise
 
 
 class _FusedVoxelRoIPool(Function):
@@ -85,6 +86,82 @@ class _RowsLinear(Function):
         return dx, dw
 
 
+# Inference (every BatchNorm of a scale not training, no gradient required): mlps_in folds into one GEMM with bias on the voxel
+# rows as they are, and pooling + mlps_out run as ONE kernel that writes its columns of the caller's row-major buffer
+# (mgar_voxel_roi_pool_eval_fwd / mgar_voxel_roi_pool_eval_bf16_fwd, csrc/voxel_roi_pool.hip).  MGAR_VRP_EVAL_FUSE=0 (or this flag) restores the train-mode
+# kernels' path around torch's batch norm (A/B in tests and profiles).
+MGAR_VRP_EVAL_FUSE = os.environ.get("MGAR_VRP_EVAL_FUSE", "1") != "0"
+_EVAL_MAXC = 32     # channels = lanes of a half-wave, on both sides of mlps_out
+
+
+def _hooked(module):
+    return bool(module._forward_hooks or module._forward_pre_hooks)
+
+
+def _conv_bn(seq, conv_type, bn_type, n_allowed):
+    """(conv, bn) of a [point-wise conv, BatchNorm(, ReLU)] container, or None"""
+    mods = list(seq)
+    if len(mods) not in n_allowed or not (isinstance(mods[0], conv_type) and _is_pointwise(mods[0]) and isinstance(mods[1], bn_type)):
+        return None
+    if len(mods) == 3 and not isinstance(mods[2], nn.ReLU):
+        return None
+    return mods[0], mods[1]
+
+
+def eval_fuse_plan(module, k, features, xyz):
+    """Whether scale k of a NeighborVoxelSAModuleMSG runs on the inference route (NeighborVoxelSAModuleMSG._eval_scale):
+    -> (conv_in, bn_in, pos_conv, pos_bn, conv_out, bn_out, relu), or None for today's path.  Fused when the switch
+    (MGAR_VRP_EVAL_FUSE) is on, module.fused is set and it pools with max_pool, the features are 2-D fp32 or bf16 rows on the
+    device (as are the voxel centres), mlps_in[k] is [point-wise Conv1d, BatchNorm1d], mlps_pos[k] [point-wise Conv2d(3 -> C),
+    BatchNorm2d], mlps_out[k] [point-wise Conv1d, BatchNorm1d(, ReLU)], none of the three BatchNorms is training and each has
+    running statistics, C and C_out <= 32, and no gradient is required: grad mode is off, or neither the features nor a
+    parameter of these modules requires one.  A forward (pre-)hook on any of these modules or their containers keeps the scale
+    unfused, so the hook still sees its module run.  Reads nothing but attributes: no device work, no synchronisation."""
+    if not (MGAR_VRP_EVAL_FUSE and module.fused and module.pool_method == 'max_pool'):
+        return None
+    if not (features.is_cuda and xyz.is_cuda and features.ndim == 2 and features.dtype in (torch.float32, torch.bfloat16)):
+        return None
+    seqs = (module.mlps_in[k], module.mlps_pos[k], module.mlps_out[k])
+    pairs = (_conv_bn(seqs[0], nn.Conv1d, nn.BatchNorm1d, (2,)), _conv_bn(seqs[1], nn.Conv2d, nn.BatchNorm2d, (2,)),
+             _conv_bn(seqs[2], nn.Conv1d, nn.BatchNorm1d, (2, 3)))
+    if None in pairs:
+        return None
+    (conv_in, bn_in), (pos_conv, pos_bn), (conv_out, bn_out) = pairs
+    chans = conv_in.out_channels
+    if not (pos_conv.in_channels == 3 and pos_conv.out_channels == chans and conv_out.in_channels == chans
+            and conv_in.in_channels == features.shape[1] and chans <= _EVAL_MAXC and conv_out.out_channels <= _EVAL_MAXC):
+        return None
+    for bn in (bn_in, pos_bn, bn_out):
+        if bn.training or bn.running_mean is None or bn.running_var is None:
+            return None
+    mods = [m for seq in seqs for m in seq]
+    if torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for m in mods for p in m.parameters())):
+        return None
+    if any(_hooked(m) for m in mods + list(seqs) + [module.relu]):
+        return None
+    return conv_in, bn_in, pos_conv, pos_bn, conv_out, bn_out, len(seqs[2]) == 3
+
+
+def folded_mlp_in(conv, bn):
+    """mlps_in = point-wise Conv1d + eval-mode BatchNorm1d as one GEMM with bias on rows: -> {dtype: (W', b)} for float32 and
+    bfloat16 rows, feats_in = features W'^T + b.  (s, b) = sparse_ops.fold_bn(bn, conv.bias); W' = s[:, None] * W formed in float64
+    and rounded once to fp32; the bf16 pair is that pair rounded once more (operands and bias of a bf16 GEMM).  Cached on the
+    convolution under the weight's _version / data_ptr and the identity of fold_bn's own cached pair: an in-place update of any
+    tensor read recomputes, a second forward launches nothing."""
+    from .....sparse_ops import fold_bn
+    scale, shift = fold_bn(bn, conv.bias)
+    key = (conv.weight._version, conv.weight.data_ptr(), conv.weight.device, id(scale), id(shift))
+    cached = conv.__dict__.get("_mgar_folded_in")
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    with torch.no_grad(), torch.autocast(device_type=conv.weight.device.type, enabled=False):
+        w = conv.weight.detach().view(conv.out_channels, conv.in_channels).double()
+        w = (scale.double()[:, None] * w).float().contiguous()
+        folded = {torch.float32: (w, shift), torch.bfloat16: (w.to(torch.bfloat16), shift.to(torch.bfloat16))}
+    conv.__dict__["_mgar_folded_in"] = (key, folded, scale, shift)   # scale / shift held: their ids stay theirs while cached
+    return folded
+
+
 class NeighborVoxelSAModuleMSG(nn.Module):
     def __init__(self, *, query_ranges: List[List[int]], radii: List[float],
                  nsamples: List[int], mlps: List[List[int]], use_xyz: bool = True, pool_method='max_pool'):
@@ -120,7 +197,8 @@ class NeighborVoxelSAModuleMSG(nn.Module):
     def _mlp_in_rows(self, k, features):
         """mlps_in[k] = Conv1d(1x1, no bias) + BatchNorm1d on ALL voxels (reference voxel_pool_modules.py:86-88), evaluated on
         the row-major (N, C) features as they are: one GEMM + the row-major BatchNorm kernels (csrc/channels_last.hpp), without
-        the two transposing copies of the (1, C, N) formulation (7.6 + 6 ms per step at config c3).  Device + train mode only.
+        the two transposing copies of the (1, C, N) formulation (7.6 + 6 ms per step at config c3).  Device + train mode only: a
+        scale whose BatchNorms are all in eval mode takes the inference route instead (eval_fuse_plan, _eval_scale).
         bf16 rows (the bf16 trunk, forward only): one bf16 GEMM, then the bf16 row-major BatchNorm -- the (N, C) bf16 result is what
         mgar_voxel_roi_pool_fwd_bf16 reads."""
         conv, bn = self.mlps_in[k][0], self.mlps_in[k][1]
@@ -137,13 +215,60 @@ class NeighborVoxelSAModuleMSG(nn.Module):
         z = _RowsLinear.apply(features.contiguous(), w)   # (N, C)
         return bn_act_rows(z, bn, False) if z.dtype == torch.float32 else None   # under autocast z is bf16: the caller's formulation
 
-    def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, new_coords, features, voxel2point_indices):
+    def _eval_scale(self, k, plan, xyz, new_xyz, new_coords, features, voxel2point_indices, out):
+        """Scale k on the inference route into out (M, C_out), rows of the features' dtype or a column slice of a wider buffer:
+        one GEMM with bias for mlps_in on all voxels, the voxel query, one kernel for everything behind it.  Autocast is
+        switched off inside: the precision is the features' own."""
+        conv_in, bn_in, pos_conv, pos_bn, conv_out, bn_out, relu = plan
+        from .....sparse_ops import fold_bn
+        grouper = self.groupers[k]
+        chans, c_out = conv_in.out_channels, conv_out.out_channels
+        with torch.no_grad(), torch.autocast(device_type=features.device.type, enabled=False):
+            w_in, b_in = folded_mlp_in(conv_in, bn_in)[features.dtype]
+            feats_in = torch.addmm(b_in, features.detach(), w_in.t())                                # (N, C)
+            idx_raw = voxel_query_utils.voxel_query_raw(grouper.max_range, grouper.radius, grouper.nsample, xyz, new_xyz,
+                                                        new_coords, voxel2point_indices)
+            pos_scale, pos_shift = fold_bn(pos_bn, pos_conv.bias)
+            out_scale, out_shift = fold_bn(bn_out, conv_out.bias)
+            pointnet2.voxel_roi_pool_eval_fwd(idx_raw.shape[0], idx_raw.shape[1], chans, c_out, xyz.contiguous(), new_xyz.contiguous(),
+                                              feats_in, idx_raw, pos_conv.weight.detach().view(chans, 3).float().contiguous(),
+                                              pos_scale, pos_shift, conv_out.weight.detach().view(c_out, chans).float().contiguous(),
+                                              out_scale, out_shift, relu, out)
+
+    def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, new_coords, features, voxel2point_indices, out=None):
         """xyz (N, 3) voxel centres, features (N, C_in), new_xyz (M, 3) grid points,
         new_coords (M, 4) [b, x, y, z] -> (M, sum_k mlps[k][-1]).
+        out: optional (M, sum_k mlps[k][-1]) row-major result buffer of the features' dtype, or a column slice of a wider one;
+        every scale on the inference route (eval_fuse_plan) writes its columns there directly, and without `out` the module
+        allocates the buffer itself -- no torch.cat either way.
         Reference: voxel_pool_modules.py:70-130."""
         new_coords = new_coords[:, [0, 3, 2, 1]].contiguous()  # -> [b, z, y, x]
+        plans = [eval_fuse_plan(self, k, features, xyz) for k in range(len(self.groupers))]
+        if plans and all(p is not None for p in plans):
+            widths = [p[4].out_channels for p in plans]
+            if out is None:
+                out = torch.empty((new_xyz.shape[0], sum(widths)), dtype=features.dtype, device=features.device)
+            elif tuple(out.shape) != (new_xyz.shape[0], sum(widths)) or out.dtype != features.dtype:
+                raise ValueError("NeighborVoxelSAModuleMSG: out must be (%d, %d) of %s" % (new_xyz.shape[0], sum(widths), features.dtype))
+            col = 0
+            for k, plan in enumerate(plans):
+                self._eval_scale(k, plan, xyz, new_xyz, new_coords, features, voxel2point_indices, out[:, col:col + widths[k]])
+                col += widths[k]
+            return out
+        result = self._forward_scales(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, new_coords, features, voxel2point_indices, plans)
+        if out is None:
+            return result
+        out.copy_(result)
+        return out
+
+    def _forward_scales(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, new_coords, features, voxel2point_indices, plans):
         per_scale = []
         for k, grouper in enumerate(self.groupers):
+            if plans[k] is not None:       # some but not all scales on the inference route: its own (M, C_out), joined below
+                part = torch.empty((new_xyz.shape[0], plans[k][4].out_channels), dtype=features.dtype, device=features.device)
+                self._eval_scale(k, plans[k], xyz, new_xyz, new_coords, features, voxel2point_indices, part)
+                per_scale.append(part)
+                continue
             feats_in = self._mlp_in_rows(k, features)
             if feats_in is None:
                 feats_in = self.mlps_in[k](features.permute(1, 0).unsqueeze(0))    # (1, C, N)
