@@ -31,7 +31,7 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
-#define MGAR_ABI_VERSION 19   /* bumped on any signature change; mgar_abi_version() returns it */
+#define MGAR_ABI_VERSION 20   /* bumped on any signature change; mgar_abi_version() returns it */
 
 /* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
@@ -528,6 +528,18 @@ int mgar_stem_conv3d_fwd(const float *x, int N, int T, int H, int W, const float
  * 3-tap and a 4-tap stride-1 convolution, Winograd F(2, 3) on the 3-tap parts: 10 instead of 14 multiply-accumulates per
  * (kt, c, kh) and output pair); 0 switches it off (A/B tests), default 1. */
 int mgar_stem_conv3d_set_minimal_filtering(int on);
+/* mgar_stem_conv3d_fwd / mgar_stem_conv3d_fwd_bf16 with an eval-mode BatchNorm [+ ReLU] in the store of whichever kernel the plain
+ * entry chooses (direct fp32, minimal filtering by W % 4 and the switch above, bf16 MFMA):  with acc the value the plain entry
+ * stores (same sum, same order),
+ *   v = fmaf(acc, scale[co], shift[co]);   y = relu ? (v > 0 ? v : (v != v ? v : +0)) : v
+ * -- a NaN passes the ReLU, a negative or -0 pre-activation gives +0; a bf16 payload is rounded once, after the activation.
+ * scale, shift (64) fp32, both required.  Sizes, workspace, timer row and refusals (bad sizes / a null pointer with N > 0
+ * MGAR_EINVAL before any device call; N == 0 MGAR_OK, nothing launched) are those of the plain entries.  The bf16 entry is called
+ * by name (not a `_bf16` twin).  Forward only. */
+int mgar_stem_conv3d_fwd_affine(const float *x, int N, int T, int H, int W, const float *w, float *w_packed, const float *scale,
+                                const float *shift, int relu, float *y, void *stream);
+int mgar_stem_conv3d_bf16_fwd_affine(const void *x, int N, int T, int H, int W, const float *w, float *w_packed, const float *scale,
+                                     const float *shift, int relu, void *y, void *stream);
 
 /* The 3x3x3, stride-1, "same"-padded convolutions of Inception-I3D (model/backbone.py:311-312 ``Conv3d_2c_3x3`` and the
  * ``Conv3d_0b_3x3`` units of every InceptionModule :215-236; Unit3D :134-206 = pad + nn.Conv3d(bias=False)) on the fp32 MFMA
@@ -549,6 +561,22 @@ int mgar_conv3d_k3_fwd(const float *x, int N, int Cin, int D, int H, int W, cons
 long long mgar_conv3d_k3_bf16_workspace_bytes(int Cin, int Cout);
 int mgar_conv3d_k3_bf16_fwd(const void *x, int N, int Cin, int D, int H, int W, const float *w, int Cout,
                             void *w_packed, void *y, void *stream);
+/* mgar_conv3d_k3_fwd / mgar_conv3d_k3_bf16_fwd with an eval-mode BatchNorm [+ ReLU] in the store and a strided destination.  With
+ * acc the value the plain entry stores (fp32: the output-transformed pair; bf16: the fp32 accumulator, before its one rounding;
+ * same sum, same order):
+ *   v = fmaf(acc, scale[co], shift[co]);   y = relu ? (v > 0 ? v : (v != v ? v : +0)) : v
+ * -- a NaN passes the ReLU, a negative or -0 pre-activation gives +0; the bf16 entry rounds once, after the activation.
+ * scale, shift (Cout) fp32, both required.  y_batch_stride: ELEMENTS between consecutive samples of y, >= Cout * D * H * W and
+ * even: y may be the channel slice Y[:, c0 : c0 + Cout] of a wider contiguous NCDHW tensor (an Inception module's concatenated
+ * output); the channel stride stays D * H * W.  The fp32 kernel stores 8-byte pairs: y must be 8-byte aligned (bf16: 2-byte).
+ * Sizes, workspace, timer rows, batch independence and refusals are those of the plain entries; a misaligned y, an odd or
+ * too-small y_batch_stride and a null pointer with N > 0 return MGAR_EINVAL before any device call; N == 0 returns MGAR_OK with
+ * nothing launched.  Forward only; the bf16 entry is called by name. */
+int mgar_conv3d_k3_fwd_affine(const float *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, float *w_packed,
+                              const float *scale, const float *shift, int relu, float *y, long long y_batch_stride, void *stream);
+int mgar_conv3d_k3_bf16_fwd_affine(const void *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, void *w_packed,
+                                   const float *scale, const float *shift, int relu, void *y, long long y_batch_stride,
+                                   void *stream);
 
 /* ===================== third-party ops on the hot path ================================ */
 

@@ -58,6 +58,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_buffer(const void *p, 
     return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 
+// The eval-mode BatchNorm [+ ReLU] epilogue of the dense convolutions' AFF instantiations (csrc/conv3d_wino.hip, conv3d_bf16.hip,
+// stem_conv.hip) -- the one written for the sparse convolution (csrc/sparse_conv.hip, sc_affine): v = fma(acc, scale[c], shift[c]),
+// then relu ? max(v, +0) with a NaN passed through : v.  A negative or -0 pre-activation gives +0.
+__device__ __forceinline__ float conv_affine(float acc, float scale, float shift, int relu) {
+    const float v = __builtin_fmaf(acc, scale, shift);
+    return relu ? (v > 0.f ? v : (v != v ? v : 0.f)) : v;
+}
+
 void set_error(const char *msg);
 
 // ---- optional per-kernel timing (bench.py's roofline table) --------------------------------------

@@ -62,11 +62,21 @@ struct CbArgs {
     long long total;
 };
 
+struct CbEpilogue {                                    // mgar_conv3d_k3_bf16_fwd_affine: scale, shift (Cout), the ReLU flag, elements between samples of y
+    const float *scale, *shift;
+    int relu;
+    long long y_batch_stride;
+};
+
 // wp: [cg][c_in group][step 14][mb 2][half 2][co 32][ci 8] bf16 (conv3d_bf16_pack_kernel)
 // NMB: 32-channel blocks per workgroup that exist (2; 1 for a tail group of <= 32 channels, launched separately)
-template <int PW, int NMB>
+// AFF: the store applies conv_affine to the fp32 accumulator BEFORE the one rounding, with the channel's scale / shift, and sample n
+// starts at y + n * e.y_batch_stride (a channel slice of a wider tensor).  The store loop runs channel block by channel block and
+// loads the block's 16 scale / shift values at the head of its pass (32 independent loads behind one wait, shared by both pixel
+// blocks; not a load-to-store dependency per element); the plain instantiations keep their loop and read nothing of `e`.
+template <int PW, int NMB, bool AFF>
 __global__ __launch_bounds__(256) void conv3d_bf16_kernel(const uint16_t *__restrict__ x, const u32x4 *__restrict__ wp, CbArgs a,
-                                                          uint16_t *__restrict__ y) {
+                                                          CbEpilogue e, uint16_t *__restrict__ y) {
     typedef CbGeom<PW> G;
     __shared__ __attribute__((aligned(16))) u32x4 s_in[2][G::IN_VEC];
     __shared__ __attribute__((aligned(16))) u32x4 s_w[2][CB_W_VEC];
@@ -189,18 +199,44 @@ __global__ __launch_bounds__(256) void conv3d_bf16_kernel(const uint16_t *__rest
 
     // store: register r of a lane is (co = 32 mb + (r & 3) + 8 (r >> 2) + 4 half, pixel l); one rounding, fp32 -> bf16
     const int wo = w0 + pcol;
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-        const int ho = h0 + prow + nb * G::BH;
-        if (ho >= a.H || wo >= a.W) continue;
+    if constexpr (AFF) {
 #pragma unroll
         for (int mb = 0; mb < NMB; ++mb) {
+            float sc[16], sh[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = cg * CB_CG + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (co >= a.Cout) continue;
-                y[(((long long)n * a.Cout + co) * a.D + d) * HW + (long long)ho * a.W + wo] =
-                    (uint16_t)(pack_bf16x2(acc[mb][nb][r], 0.f) & 0xffffu);
+            for (int r = 0; r < 16; ++r) {                 // (a channel beyond Cout reads the last one's: never stored)
+                const int cc = min(cg * CB_CG + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, a.Cout - 1);
+                sc[r] = e.scale[cc];
+                sh[r] = e.shift[cc];
+            }
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                const int ho = h0 + prow + nb * G::BH;
+                if (ho >= a.H || wo >= a.W) continue;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = cg * CB_CG + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    if (co >= a.Cout) continue;
+                    const float v = conv_affine(acc[mb][nb][r], sc[r], sh[r], e.relu);
+                    y[(long long)n * e.y_batch_stride + ((long long)co * a.D + d) * HW + (long long)ho * a.W + wo] =
+                        (uint16_t)(pack_bf16x2(v, 0.f) & 0xffffu);
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int ho = h0 + prow + nb * G::BH;
+            if (ho >= a.H || wo >= a.W) continue;
+#pragma unroll
+            for (int mb = 0; mb < NMB; ++mb) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = cg * CB_CG + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    if (co >= a.Cout) continue;
+                    y[(((long long)n * a.Cout + co) * a.D + d) * HW + (long long)ho * a.W + wo] =
+                        (uint16_t)(pack_bf16x2(acc[mb][nb][r], 0.f) & 0xffffu);
+                }
             }
         }
     }
@@ -222,8 +258,8 @@ __global__ void conv3d_bf16_pack_kernel(const float *__restrict__ w, int Cin, in
     wp[e] = (uint16_t)(pack_bf16x2(v, 0.f) & 0xffffu);
 }
 
-template <int PW>
-static void cb_launch(const uint16_t *x, const u32x4 *wp, CbArgs a, uint16_t *y, hipStream_t st) {
+template <int PW, bool AFF>
+static void cb_launch(const uint16_t *x, const u32x4 *wp, CbArgs a, CbEpilogue e, uint16_t *y, hipStream_t st) {
     typedef CbGeom<PW> G;
     a.tiles_w = ceil_div(a.W, G::TW);
     a.tiles_h = ceil_div(a.H, G::TH);
@@ -234,13 +270,13 @@ static void cb_launch(const uint16_t *x, const u32x4 *wp, CbArgs a, uint16_t *y,
         a.cg0 = 0; a.ncg = groups - tail;
         a.total = tiles * a.ncg;
         a.per_xcd = (int)((a.total + 7) / 8);
-        hipLaunchKernelGGL((conv3d_bf16_kernel<PW, 2>), dim3(a.per_xcd * 8), dim3(256), 0, st, x, wp, a, y);
+        hipLaunchKernelGGL((conv3d_bf16_kernel<PW, 2, AFF>), dim3(a.per_xcd * 8), dim3(256), 0, st, x, wp, a, e, y);
     }
     if (tail) {
         a.cg0 = groups - 1; a.ncg = 1;
         a.total = tiles;
         a.per_xcd = (int)((a.total + 7) / 8);
-        hipLaunchKernelGGL((conv3d_bf16_kernel<PW, 1>), dim3(a.per_xcd * 8), dim3(256), 0, st, x, wp, a, y);
+        hipLaunchKernelGGL((conv3d_bf16_kernel<PW, 1, AFF>), dim3(a.per_xcd * 8), dim3(256), 0, st, x, wp, a, e, y);
     }
 }
 
@@ -255,20 +291,13 @@ MGAR_API long long mgar_conv3d_k3_bf16_workspace_bytes(int Cin, int Cout) {
     return (long long)ceil_div(Cout, CB_CG) * ceil_div(Cin, CB_CI) * CB_W_VEC * 16;
 }
 
-// x (N, Cin, D, H, W) bf16 NCDHW, w (Cout, Cin, 3, 3, 3) fp32 -> y (N, Cout, D, H, W) bf16: stride 1, zero padding 1 on every
-// side.  Cin % 8 == 0 and even W (every I3D instance); anything else is MGAR_EINVAL and the caller keeps the library convolution.
-MGAR_API int mgar_conv3d_k3_bf16_fwd(const void *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, void *w_packed,
-                                     void *y, void *stream) {
-    MGAR_REQUIRE(N >= 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "conv3d_k3_bf16_fwd: bad sizes");
-    MGAR_REQUIRE(Cin % CB_CI == 0 && W % 2 == 0, "conv3d_k3_bf16_fwd: Cin must be a multiple of 8 and W even");
-    if (N == 0) return MGAR_OK;
-    MGAR_REQUIRE(x && w && w_packed && y, "conv3d_k3_bf16_fwd: null pointer");
-    MGAR_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 1) == 0 && ((uintptr_t)w_packed & 15) == 0,
-                 "conv3d_k3_bf16_fwd: x must be 4-byte, w_packed 16-byte aligned");
-    MGAR_REQUIRE((long long)2 * CB_CI * D * H * W < (1ll << 31), "conv3d_k3_bf16_fwd: volume too large for 32-bit tile offsets");
+// The two entry points below: AFF = false, mgar_conv3d_k3_bf16_fwd (e unused); AFF = true, mgar_conv3d_k3_bf16_fwd_affine.  Same
+// packing, same tile choice, same timer row.
+template <bool AFF>
+static int cb_forward(const char *who, const void *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, void *w_packed,
+                      CbEpilogue e, void *y, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     CbArgs a{N, Cin, D, H, W, Cout, ceil_div(Cout, CB_CG), 0, 0, 0, 0, 0};
-    MGAR_REQUIRE((long long)a.ncg * ceil_div(W, 8) * ceil_div(H, 8) * D * N < (1ll << 30), "conv3d_k3_bf16_fwd: too many tiles");
     const long long wtotal = (long long)a.ncg * (Cin / CB_CI) * CB_W_VEC * 8;    // bf16 elements
     hipLaunchKernelGGL(conv3d_bf16_pack_kernel, dim3(ceil_div(wtotal, 256)), dim3(256), 0, st, w, Cin, Cout, wtotal, (uint16_t *)w_packed);
     // the tile shape that wastes the fewest outputs (ties: the widest rows)
@@ -283,9 +312,44 @@ MGAR_API int mgar_conv3d_k3_bf16_fwd(const void *x, int N, int Cin, int D, int H
         const uint16_t *xp = (const uint16_t *)x;
         const u32x4 *wv = (const u32x4 *)w_packed;
         uint16_t *yp = (uint16_t *)y;
-        if (best == 32) cb_launch<32>(xp, wv, a, yp, st);
-        else if (best == 16) cb_launch<16>(xp, wv, a, yp, st);
-        else cb_launch<8>(xp, wv, a, yp, st);
+        if (best == 32) cb_launch<32, AFF>(xp, wv, a, e, yp, st);
+        else if (best == 16) cb_launch<16, AFF>(xp, wv, a, e, yp, st);
+        else cb_launch<8, AFF>(xp, wv, a, e, yp, st);
     }
-    return check_launch("conv3d_k3_bf16_fwd: launch failed");
+    return check_launch(who);
+}
+
+// x (N, Cin, D, H, W) bf16 NCDHW, w (Cout, Cin, 3, 3, 3) fp32 -> y (N, Cout, D, H, W) bf16: stride 1, zero padding 1 on every
+// side.  Cin % 8 == 0 and even W (every I3D instance); anything else is MGAR_EINVAL and the caller keeps the library convolution.
+MGAR_API int mgar_conv3d_k3_bf16_fwd(const void *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, void *w_packed,
+                                     void *y, void *stream) {
+    MGAR_REQUIRE(N >= 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "conv3d_k3_bf16_fwd: bad sizes");
+    MGAR_REQUIRE(Cin % CB_CI == 0 && W % 2 == 0, "conv3d_k3_bf16_fwd: Cin must be a multiple of 8 and W even");
+    if (N == 0) return MGAR_OK;
+    MGAR_REQUIRE(x && w && w_packed && y, "conv3d_k3_bf16_fwd: null pointer");
+    MGAR_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 1) == 0 && ((uintptr_t)w_packed & 15) == 0,
+                 "conv3d_k3_bf16_fwd: x must be 4-byte, w_packed 16-byte aligned");
+    MGAR_REQUIRE((long long)2 * CB_CI * D * H * W < (1ll << 31), "conv3d_k3_bf16_fwd: volume too large for 32-bit tile offsets");
+    MGAR_REQUIRE((long long)ceil_div(Cout, CB_CG) * ceil_div(W, 8) * ceil_div(H, 8) * D * N < (1ll << 30), "conv3d_k3_bf16_fwd: too many tiles");
+    return cb_forward<false>("conv3d_k3_bf16_fwd: launch failed", x, N, Cin, D, H, W, w, Cout, w_packed, CbEpilogue{nullptr, nullptr, 0, 0}, y, stream);
+}
+
+// mgar_conv3d_k3_bf16_fwd with the eval-mode BatchNorm [+ ReLU] epilogue applied to the fp32 accumulator before the one rounding:
+// y = bf16(conv_affine(acc, scale[co], shift[co], relu)).  scale, shift (Cout) fp32, both required; y_batch_stride in ELEMENTS
+// (>= Cout * D * H * W, even) as in mgar_conv3d_k3_fwd_affine: y may be a channel slice of a wider contiguous NCDHW tensor.
+MGAR_API int mgar_conv3d_k3_bf16_fwd_affine(const void *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, void *w_packed,
+                                            const float *scale, const float *shift, int relu, void *y, long long y_batch_stride,
+                                            void *stream) {
+    MGAR_REQUIRE(N >= 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "conv3d_k3_bf16_fwd_affine: bad sizes");
+    MGAR_REQUIRE(Cin % CB_CI == 0 && W % 2 == 0, "conv3d_k3_bf16_fwd_affine: Cin must be a multiple of 8 and W even");
+    if (N == 0) return MGAR_OK;
+    MGAR_REQUIRE(x && w && w_packed && scale && shift && y, "conv3d_k3_bf16_fwd_affine: null pointer");
+    MGAR_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 1) == 0 && ((uintptr_t)w_packed & 15) == 0,
+                 "conv3d_k3_bf16_fwd_affine: x must be 4-byte, y 2-byte, w_packed 16-byte aligned");
+    MGAR_REQUIRE(y_batch_stride % 2 == 0 && y_batch_stride >= (long long)Cout * D * H * W,
+                 "conv3d_k3_bf16_fwd_affine: y_batch_stride must be even and at least Cout * D * H * W");
+    MGAR_REQUIRE((long long)2 * CB_CI * D * H * W < (1ll << 31), "conv3d_k3_bf16_fwd_affine: volume too large for 32-bit tile offsets");
+    MGAR_REQUIRE((long long)ceil_div(Cout, CB_CG) * ceil_div(W, 8) * ceil_div(H, 8) * D * N < (1ll << 30), "conv3d_k3_bf16_fwd_affine: too many tiles");
+    return cb_forward<true>("conv3d_k3_bf16_fwd_affine: launch failed", x, N, Cin, D, H, W, w, Cout, w_packed,
+                            CbEpilogue{scale, shift, relu ? 1 : 0, y_batch_stride}, y, stream);
 }

@@ -57,11 +57,21 @@ struct CwArgs {
     long long total;
 };
 
+struct CwEpilogue {                                // mgar_conv3d_k3_fwd_affine: scale, shift (Cout), the ReLU flag, elements between samples of y
+    const float *scale, *shift;
+    int relu;
+    long long y_batch_stride;
+};
+
 // wt: [cg][c_in pair][kd*3+kh][half][co 64][t 4] (conv3d_wino_filter_kernel)
 // NMB: 32-channel blocks per workgroup that exist (2; 1 for a tail group of <= 32 channels, launched separately)
-template <int PW, int NMB>
+// AFF: the store applies conv_affine to the output-transformed pair with the channel's scale / shift and sample n starts at
+// y + n * e.y_batch_stride (a channel slice of a wider tensor).  The 16 scale / shift values of a channel block are loaded inside the
+// store loop, at the head of the block's pass -- 32 independent loads behind one wait instead of a load-to-store dependency per row;
+// nothing of the epilogue is live under the MFMAs.  The plain instantiations read nothing of `e`.
+template <int PW, int NMB, bool AFF>
 __global__ __launch_bounds__(256, 2) void conv3d_wino_kernel(const float *__restrict__ x, const float *__restrict__ wt, CwArgs a,
-                                                             float *__restrict__ y) {
+                                                             CwEpilogue e, float *__restrict__ y) {
     typedef CwGeom<PW> G;
     // (padded to a whole number of elements per thread: the staging loops carry no guards -- a guarded store lets the compiler
     // sink the global load down to it, behind the MFMA block, and the prefetch is gone)
@@ -185,6 +195,15 @@ __global__ __launch_bounds__(256, 2) void conv3d_wino_kernel(const float *__rest
     if (ho < a.H && wo < a.W) {
 #pragma unroll
         for (int mb = 0; mb < NMB; ++mb) {
+            [[maybe_unused]] float sc[16], sh[16];
+            if constexpr (AFF) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {             // (a channel beyond Cout reads the last one's: never stored)
+                    const int cc = min(cg * CW_CG + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, a.Cout - 1);
+                    sc[r] = e.scale[cc];
+                    sh[r] = e.shift[cc];
+                }
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = cg * CW_CG + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
@@ -193,7 +212,13 @@ __global__ __launch_bounds__(256, 2) void conv3d_wino_kernel(const float *__rest
                 f32x2 o;
                 o.x = (m0 + m1) + m2;
                 o.y = (m1 - m2) - m3;
-                *reinterpret_cast<f32x2 *>(y + (((long long)n * a.Cout + co) * a.D + d) * HW + (long long)ho * a.W + wo) = o;
+                if constexpr (AFF) {
+                    o.x = conv_affine(o.x, sc[r], sh[r], e.relu);
+                    o.y = conv_affine(o.y, sc[r], sh[r], e.relu);
+                    *reinterpret_cast<f32x2 *>(y + (long long)n * e.y_batch_stride + ((long long)co * a.D + d) * HW + (long long)ho * a.W + wo) = o;
+                } else {
+                    *reinterpret_cast<f32x2 *>(y + (((long long)n * a.Cout + co) * a.D + d) * HW + (long long)ho * a.W + wo) = o;
+                }
             }
         }
     }
@@ -226,8 +251,8 @@ __global__ void conv3d_wino_filter_kernel(const float *__restrict__ w, int Cin, 
 // a concurrent HBM-bound stream then runs beside this MFMA-bound kernel).  0 by default.
 static int g_cw_lds_pad = 0;
 
-template <int PW>
-static void cw_launch(const float *x, const float *wt, CwArgs a, float *y, hipStream_t st) {
+template <int PW, bool AFF>
+static void cw_launch(const float *x, const float *wt, CwArgs a, CwEpilogue e, float *y, hipStream_t st) {
     typedef CwGeom<PW> G;
     a.tiles_w = ceil_div(a.W, G::TW);
     a.tiles_h = ceil_div(a.H, G::TH);
@@ -238,13 +263,13 @@ static void cw_launch(const float *x, const float *wt, CwArgs a, float *y, hipSt
         a.cg0 = 0; a.ncg = groups - tail;
         a.total = tiles * a.ncg;
         a.per_xcd = (int)((a.total + 7) / 8);
-        hipLaunchKernelGGL((conv3d_wino_kernel<PW, 2>), dim3(a.per_xcd * 8), dim3(256), g_cw_lds_pad, st, x, wt, a, y);
+        hipLaunchKernelGGL((conv3d_wino_kernel<PW, 2, AFF>), dim3(a.per_xcd * 8), dim3(256), g_cw_lds_pad, st, x, wt, a, e, y);
     }
     if (tail) {
         a.cg0 = groups - 1; a.ncg = 1;
         a.total = tiles;
         a.per_xcd = (int)((a.total + 7) / 8);
-        hipLaunchKernelGGL((conv3d_wino_kernel<PW, 1>), dim3(a.per_xcd * 8), dim3(256), g_cw_lds_pad, st, x, wt, a, y);
+        hipLaunchKernelGGL((conv3d_wino_kernel<PW, 1, AFF>), dim3(a.per_xcd * 8), dim3(256), g_cw_lds_pad, st, x, wt, a, e, y);
     }
 }
 
@@ -264,19 +289,14 @@ MGAR_API int mgar_conv3d_k3_set_lds_pad(int bytes) {
     return MGAR_OK;
 }
 
-// x (N, Cin, D, H, W) fp32 NCDHW, w (Cout, Cin, 3, 3, 3) -> y (N, Cout, D, H, W): stride 1, zero padding 1 on every side.
-// Cin and W must be even (every I3D instance is); anything else is MGAR_EINVAL and the caller keeps the library convolution.
-MGAR_API int mgar_conv3d_k3_fwd(const float *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, float *w_packed, float *y,
-                                void *stream) {
-    MGAR_REQUIRE(N >= 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "conv3d_k3_fwd: bad sizes");
-    MGAR_REQUIRE(Cin % 2 == 0 && W % 2 == 0, "conv3d_k3_fwd: Cin and W must be even");
-    if (N == 0) return MGAR_OK;
-    MGAR_REQUIRE(x && w && w_packed && y, "conv3d_k3_fwd: null pointer");
-    MGAR_REQUIRE((long long)8 * D * H * W < (1ll << 31), "conv3d_k3_fwd: volume too large for 32-bit tile offsets");
+// The two entry points below: AFF = false, mgar_conv3d_k3_fwd (e unused); AFF = true, mgar_conv3d_k3_fwd_affine.  Same filter
+// transform, same tile choice, same timer row.
+template <bool AFF>
+static int cw_forward(const char *who, const float *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, float *w_packed,
+                      CwEpilogue e, float *y, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     CwArgs a{N, Cin, D, H, W, Cout, ceil_div(Cout, CW_CG), 0, 0, 0, 0, 0};
     const long long wtotal = (long long)a.ncg * (Cin / 2) * 9 * 2 * CW_CG;      // float4 elements
-    MGAR_REQUIRE((long long)a.ncg * ceil_div(W, 16) * ceil_div(H, 4) * D * N < (1ll << 30), "conv3d_k3_fwd: too many tiles");
     hipLaunchKernelGGL(conv3d_wino_filter_kernel, dim3(ceil_div(wtotal, 256)), dim3(256), 0, st, w, Cin, Cout, wtotal, w_packed);
     // the tile shape that wastes the fewest outputs (ties: the widest rows)
     auto padded = [&](int pw) { return (long long)ceil_div(W, 2 * pw) * 2 * pw * ceil_div(H, 128 / pw) * (128 / pw); };
@@ -287,9 +307,42 @@ MGAR_API int mgar_conv3d_k3_fwd(const float *x, int N, int Cin, int D, int H, in
     {
         // bytes: input + output once; flops: the MFMA work actually issued = 2/3 of the direct convolution's 2 * 27 * Cin * Cout per output
         KtScope kt(KT_CONV3D_WINO, st, 4.0 * outs * (Cin + Cout), 2.0 * outs * Cout * Cin * 18.0);
-        if (best == 32) cw_launch<32>(x, w_packed, a, y, st);
-        else if (best == 16) cw_launch<16>(x, w_packed, a, y, st);
-        else cw_launch<8>(x, w_packed, a, y, st);
+        if (best == 32) cw_launch<32, AFF>(x, w_packed, a, e, y, st);
+        else if (best == 16) cw_launch<16, AFF>(x, w_packed, a, e, y, st);
+        else cw_launch<8, AFF>(x, w_packed, a, e, y, st);
     }
-    return check_launch("conv3d_k3_fwd: launch failed");
+    return check_launch(who);
+}
+
+// x (N, Cin, D, H, W) fp32 NCDHW, w (Cout, Cin, 3, 3, 3) -> y (N, Cout, D, H, W): stride 1, zero padding 1 on every side.
+// Cin and W must be even (every I3D instance is); anything else is MGAR_EINVAL and the caller keeps the library convolution.
+MGAR_API int mgar_conv3d_k3_fwd(const float *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, float *w_packed, float *y,
+                                void *stream) {
+    MGAR_REQUIRE(N >= 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "conv3d_k3_fwd: bad sizes");
+    MGAR_REQUIRE(Cin % 2 == 0 && W % 2 == 0, "conv3d_k3_fwd: Cin and W must be even");
+    if (N == 0) return MGAR_OK;
+    MGAR_REQUIRE(x && w && w_packed && y, "conv3d_k3_fwd: null pointer");
+    MGAR_REQUIRE((long long)8 * D * H * W < (1ll << 31), "conv3d_k3_fwd: volume too large for 32-bit tile offsets");
+    MGAR_REQUIRE((long long)ceil_div(Cout, CW_CG) * ceil_div(W, 16) * ceil_div(H, 4) * D * N < (1ll << 30), "conv3d_k3_fwd: too many tiles");
+    return cw_forward<false>("conv3d_k3_fwd: launch failed", x, N, Cin, D, H, W, w, Cout, w_packed, CwEpilogue{nullptr, nullptr, 0, 0}, y, stream);
+}
+
+// mgar_conv3d_k3_fwd with the eval-mode BatchNorm [+ ReLU] epilogue in its store: with o the output-transformed value the plain
+// entry stores (same sum, same order), y = conv_affine(o, scale[co], shift[co], relu).  scale, shift (Cout) fp32, both required.
+// Sample n of y starts y_batch_stride ELEMENTS after sample n - 1 (>= Cout * D * H * W, even; y 8-byte aligned: the kernel stores
+// pairs): y may be the channel slice Y[:, c0 : c0 + Cout] of a wider contiguous NCDHW tensor; the channel stride stays D * H * W.
+MGAR_API int mgar_conv3d_k3_fwd_affine(const float *x, int N, int Cin, int D, int H, int W, const float *w, int Cout, float *w_packed,
+                                       const float *scale, const float *shift, int relu, float *y, long long y_batch_stride,
+                                       void *stream) {
+    MGAR_REQUIRE(N >= 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "conv3d_k3_fwd_affine: bad sizes");
+    MGAR_REQUIRE(Cin % 2 == 0 && W % 2 == 0, "conv3d_k3_fwd_affine: Cin and W must be even");
+    if (N == 0) return MGAR_OK;
+    MGAR_REQUIRE(x && w && w_packed && scale && shift && y, "conv3d_k3_fwd_affine: null pointer");
+    MGAR_REQUIRE(((uintptr_t)y & 7) == 0, "conv3d_k3_fwd_affine: y must be 8-byte aligned");
+    MGAR_REQUIRE(y_batch_stride % 2 == 0 && y_batch_stride >= (long long)Cout * D * H * W,
+                 "conv3d_k3_fwd_affine: y_batch_stride must be even and at least Cout * D * H * W");
+    MGAR_REQUIRE((long long)8 * D * H * W < (1ll << 31), "conv3d_k3_fwd_affine: volume too large for 32-bit tile offsets");
+    MGAR_REQUIRE((long long)ceil_div(Cout, CW_CG) * ceil_div(W, 16) * ceil_div(H, 4) * D * N < (1ll << 30), "conv3d_k3_fwd_affine: too many tiles");
+    return cw_forward<true>("conv3d_k3_fwd_affine: launch failed", x, N, Cin, D, H, W, w, Cout, w_packed,
+                            CwEpilogue{scale, shift, relu ? 1 : 0, y_batch_stride}, y, stream);
 }

@@ -42,10 +42,18 @@ struct StemArgs {
     int N, T, H, W, To, Ho, Wo, pt, ph, pw;   // front paddings of the TF "same" mode
 };
 
+// The *_affine entry points (AFF instantiations of the three kernels): the store applies conv_affine with the channel's scale /
+// shift (64 each; the 16 of a channel block are loaded inside the store loop, at the head of the block's pass), before the one
+// rounding of a bf16 payload; the plain instantiations read nothing of it.
+struct StemEpilogue {
+    const float *scale, *shift;
+    int relu;
+};
+
 // wp: weights packed as [kt][c_in][tap (50)][co (64)], tap = kh * 7 + kw, tap 49 = 0
-template <typename T>
+template <typename T, bool AFF>
 __global__ __launch_bounds__(256, 2) void stem_conv3d_kernel(const T *__restrict__ x, const float *__restrict__ wp, StemArgs a,
-                                                             T *__restrict__ y) {
+                                                             StemEpilogue ep, T *__restrict__ y) {
     __shared__ float s_in[2][SCV_IN_FLOATS];
     __shared__ __attribute__((aligned(16))) float s_w[2][SCV_W_FLOATS];
     const int tiles_w = (a.Wo + SCV_TW - 1) / SCV_TW;
@@ -130,17 +138,41 @@ __global__ __launch_bounds__(256, 2) void stem_conv3d_kernel(const T *__restrict
     }
     // D[row = co][col = l = wo]: every accumulator register is 32 consecutive output columns of one channel
     const int wo = wo0 + l;
+    if constexpr (AFF) {                                   // channel block by channel block: its 16 scale / shift values first
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-        const int ho = ho0 + 2 * wave + nb;
-        if (ho >= a.Ho || wo >= a.Wo) continue;
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
+        for (int mb = 0; mb < 2; ++mb) {
+            float sc[16], sh[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                Payload<T>::st(y + ((((size_t)n * SCV_COUT + co) * a.To + to) * a.Ho + ho) * a.Wo + wo, acc[mb][nb][r]);
+                sc[r] = ep.scale[co];
+                sh[r] = ep.shift[co];
             }
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                const int ho = ho0 + 2 * wave + nb;
+                if (ho >= a.Ho || wo >= a.Wo) continue;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    Payload<T>::st(y + ((((size_t)n * SCV_COUT + co) * a.To + to) * a.Ho + ho) * a.Wo + wo,
+                                   conv_affine(acc[mb][nb][r], sc[r], sh[r], ep.relu));
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int ho = ho0 + 2 * wave + nb;
+            if (ho >= a.Ho || wo >= a.Wo) continue;
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    Payload<T>::st(y + ((((size_t)n * SCV_COUT + co) * a.To + to) * a.Ho + ho) * a.Wo + wo, acc[mb][nb][r]);
+                }
+        }
     }
 }
 
@@ -170,8 +202,9 @@ constexpr int SCB_COLS = 72;                                              // pat
 constexpr int SCB_IN_HALVES = SCV_IH * SCB_COLS;                          // 1512
 constexpr int SCB_W_HALVES = 4 * SCV_COUT * 16;                           // 4096 per slab: [step][co][h][8]
 
+template <bool AFF>
 __global__ __launch_bounds__(256, 2) void stem_conv3d_bf16_kernel(const bf16_t *__restrict__ x, const u32x4 *__restrict__ wp, StemArgs a,
-                                                                  bf16_t *__restrict__ y) {
+                                                                  StemEpilogue ep, bf16_t *__restrict__ y) {
     __shared__ __attribute__((aligned(16))) uint16_t s_in[2][SCB_IN_HALVES];
     __shared__ __attribute__((aligned(16))) uint16_t s_w[2][SCB_W_HALVES];
     const int tiles_w = (a.Wo + SCV_TW - 1) / SCV_TW;
@@ -249,17 +282,41 @@ __global__ __launch_bounds__(256, 2) void stem_conv3d_bf16_kernel(const bf16_t *
         __syncthreads();
     }
     const int wo = wo0 + l;
+    if constexpr (AFF) {                                   // channel block by channel block: its 16 scale / shift values first
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-        const int ho = ho0 + 2 * wave + nb;
-        if (ho >= a.Ho || wo >= a.Wo) continue;
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
+        for (int mb = 0; mb < 2; ++mb) {
+            float sc[16], sh[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                Payload<bf16_t>::st(y + ((((size_t)n * SCV_COUT + co) * a.To + to) * a.Ho + ho) * a.Wo + wo, acc[mb][nb][r]);
+                sc[r] = ep.scale[co];
+                sh[r] = ep.shift[co];
             }
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                const int ho = ho0 + 2 * wave + nb;
+                if (ho >= a.Ho || wo >= a.Wo) continue;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    Payload<bf16_t>::st(y + ((((size_t)n * SCV_COUT + co) * a.To + to) * a.Ho + ho) * a.Wo + wo,
+                                   conv_affine(acc[mb][nb][r], sc[r], sh[r], ep.relu));
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int ho = ho0 + 2 * wave + nb;
+            if (ho >= a.Ho || wo >= a.Wo) continue;
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    Payload<bf16_t>::st(y + ((((size_t)n * SCV_COUT + co) * a.To + to) * a.Ho + ho) * a.Wo + wo, acc[mb][nb][r]);
+                }
+        }
     }
 }
 
@@ -305,8 +362,9 @@ constexpr int SW_W_MAIN = SCV_K * 2 * SCV_COUT * 4;                       // [kh
 constexpr int SW_W_FLOATS = SW_W_MAIN + 8 * SCV_COUT;                     // + direct tap [kh 8 (7 + a zero row)][co] = 4096
 constexpr int SW_W_PER_THREAD = SW_W_FLOATS / 4 / 256;                    // 4 x f32x4
 
+template <bool AFF>
 __global__ __launch_bounds__(256, 2) void stem_conv3d_wino_kernel(const float *__restrict__ x, const float *__restrict__ wp, StemArgs a,
-                                                                  float *__restrict__ y) {
+                                                                  StemEpilogue ep, float *__restrict__ y) {
     __shared__ __attribute__((aligned(16))) float s_in[2][SW_IN_FLOATS];
     __shared__ __attribute__((aligned(16))) float s_w[2][SW_W_FLOATS];
     const int tiles_w = (a.Wo + SW_TWO - 1) / SW_TWO;
@@ -425,7 +483,16 @@ __global__ __launch_bounds__(256, 2) void stem_conv3d_wino_kernel(const float *_
     const int ho = ho0 + wave, wo = wo0 + 2 * l;
     if (ho < a.Ho && wo < a.Wo) {
 #pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
+        for (int mb = 0; mb < 2; ++mb) {
+            [[maybe_unused]] float sc[16], sh[16];
+            if constexpr (AFF) {                           // the channel block's 16 scale / shift values first
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    sc[r] = ep.scale[co];
+                    sh[r] = ep.shift[co];
+                }
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -433,8 +500,13 @@ __global__ __launch_bounds__(256, 2) void stem_conv3d_wino_kernel(const float *_
                 f32x2 o;
                 o.x = (m0 + m1) + m2;
                 o.y = (m1 - m2) - m3;
+                if constexpr (AFF) {
+                    o.x = conv_affine(o.x, sc[r], sh[r], ep.relu);
+                    o.y = conv_affine(o.y, sc[r], sh[r], ep.relu);
+                }
                 *reinterpret_cast<f32x2 *>(y + ((((size_t)n * SCV_COUT + co) * a.To + to) * a.Ho + ho) * a.Wo + wo) = o;
             }
+        }
     }
 }
 
@@ -459,11 +531,12 @@ __global__ void stem_pack_weights_wino_kernel(const float *__restrict__ w, float
 
 static int g_stem_minimal_filtering = 1;
 
-template <typename T>
-static int stem_conv_impl(const T *x, int N, int Tn, int H, int W, const float *w, float *w_packed, T *y, void *stream) {
+// AFF = false: the plain entries (ep unused); AFF = true: the *_affine entries.  Same kernel choice, same timer row.
+template <typename T, bool AFF>
+static int stem_conv_impl(const T *x, int N, int Tn, int H, int W, const float *w, float *w_packed, StemEpilogue ep, T *y, void *stream) {
     MGAR_REQUIRE(N >= 0 && Tn > 0 && H > 0 && W > 0, "stem_conv3d_fwd: bad sizes");
     if (N == 0) return MGAR_OK;
-    MGAR_REQUIRE(x && w && w_packed && y, "stem_conv3d_fwd: null pointer");
+    MGAR_REQUIRE(x && w && w_packed && y && (!AFF || (ep.scale && ep.shift)), "stem_conv3d_fwd: null pointer");
     auto front = [](int size) {   // TF "same" for kernel 7, stride 2 (model/backbone.py:168-172)
         const int total = size % SCV_S == 0 ? SCV_K - SCV_S : SCV_K - size % SCV_S;
         return (total > 0 ? total : 0) / 2;
@@ -479,8 +552,8 @@ static int stem_conv_impl(const T *x, int N, int Tn, int H, int W, const float *
                            reinterpret_cast<uint16_t *>(w_packed));
         KtScope kt(KT_STEM_CONV, st, (double)sizeof(T) * ((double)N * SCV_CIN * Tn * H * W + outs * SCV_COUT),
                    2.0 * outs * SCV_COUT * SCV_CIN * SCV_K * SCV_K * SCV_K);
-        hipLaunchKernelGGL(stem_conv3d_bf16_kernel, dim3(tiles, a.To, N), dim3(256), 0, st, reinterpret_cast<const bf16_t *>(x),
-                           reinterpret_cast<const u32x4 *>(w_packed), a, reinterpret_cast<bf16_t *>(y));
+        hipLaunchKernelGGL(stem_conv3d_bf16_kernel<AFF>, dim3(tiles, a.To, N), dim3(256), 0, st, reinterpret_cast<const bf16_t *>(x),
+                           reinterpret_cast<const u32x4 *>(w_packed), a, ep, reinterpret_cast<bf16_t *>(y));
         return check_launch("stem_conv3d_fwd: launch failed");
     }
     if (!Payload<T>::is_bf16 && g_stem_minimal_filtering && W % 4 == 0) {      // even W (front padding 2) and whole output pairs
@@ -489,15 +562,15 @@ static int stem_conv_impl(const T *x, int N, int Tn, int H, int W, const float *
         // flops: the MFMA work issued = 10/14 of the direct convolution's (bench.py prices the kernel against the MFMA peak)
         KtScope kt(KT_STEM_CONV, st, (double)sizeof(T) * ((double)N * SCV_CIN * Tn * H * W + outs * SCV_COUT),
                    2.0 * outs * SCV_COUT * SCV_CIN * SCV_K * SCV_K * 5.0);
-        hipLaunchKernelGGL(stem_conv3d_wino_kernel, dim3(wtiles, a.To, N), dim3(256), 0, st, reinterpret_cast<const float *>(x),
-                           (const float *)w_packed, a, reinterpret_cast<float *>(y));
+        hipLaunchKernelGGL(stem_conv3d_wino_kernel<AFF>, dim3(wtiles, a.To, N), dim3(256), 0, st, reinterpret_cast<const float *>(x),
+                           (const float *)w_packed, a, ep, reinterpret_cast<float *>(y));
         return check_launch("stem_conv3d_fwd: launch failed");
     }
     hipLaunchKernelGGL(stem_pack_weights_kernel, dim3(ceil_div(SCV_K * SCV_CIN * SCV_W_FLOATS, 256)), dim3(256), 0, st, w, w_packed);
     {
         KtScope kt(KT_STEM_CONV, st, (double)sizeof(T) * ((double)N * SCV_CIN * Tn * H * W + outs * SCV_COUT),
                    2.0 * outs * SCV_COUT * SCV_CIN * SCV_K * SCV_K * SCV_K);
-        hipLaunchKernelGGL(stem_conv3d_kernel<T>, dim3(tiles, a.To, N), dim3(256), 0, st, x, (const float *)w_packed, a, y);
+        hipLaunchKernelGGL((stem_conv3d_kernel<T, AFF>), dim3(tiles, a.To, N), dim3(256), 0, st, x, (const float *)w_packed, a, ep, y);
     }
     return check_launch("stem_conv3d_fwd: launch failed");
 }
@@ -512,8 +585,19 @@ MGAR_API int mgar_stem_conv3d_workspace_floats(void) { return SCV_K * SCV_CIN * 
 // A/B switch (tests, tools): 0 = the direct kernel for fp32 too; default 1 = minimal filtering along W where W % 4 == 0
 MGAR_API int mgar_stem_conv3d_set_minimal_filtering(int on) { g_stem_minimal_filtering = on ? 1 : 0; return MGAR_OK; }
 MGAR_API int mgar_stem_conv3d_fwd(const float *x, int N, int T, int H, int W, const float *w, float *w_packed, float *y, void *stream) {
-    return stem_conv_impl<float>(x, N, T, H, W, w, w_packed, y, stream);
+    return stem_conv_impl<float, false>(x, N, T, H, W, w, w_packed, StemEpilogue{nullptr, nullptr, 0}, y, stream);
 }
 MGAR_API int mgar_stem_conv3d_fwd_bf16(const void *x, int N, int T, int H, int W, const float *w, float *w_packed, void *y, void *stream) {
-    return stem_conv_impl<bf16_t>((const bf16_t *)x, N, T, H, W, w, w_packed, (bf16_t *)y, stream);
+    return stem_conv_impl<bf16_t, false>((const bf16_t *)x, N, T, H, W, w, w_packed, StemEpilogue{nullptr, nullptr, 0}, (bf16_t *)y, stream);
+}
+// The two entries above with the eval-mode BatchNorm [+ ReLU] epilogue in the store of whichever kernel they choose (direct fp32,
+// minimal filtering, bf16 MFMA): y = conv_affine(acc, scale[co], shift[co], relu) with acc the value the plain entry stores (same
+// sum, same order); a bf16 payload is rounded once, after the activation.  scale, shift (64) fp32, both required.
+MGAR_API int mgar_stem_conv3d_fwd_affine(const float *x, int N, int T, int H, int W, const float *w, float *w_packed, const float *scale,
+                                         const float *shift, int relu, float *y, void *stream) {
+    return stem_conv_impl<float, true>(x, N, T, H, W, w, w_packed, StemEpilogue{scale, shift, relu ? 1 : 0}, y, stream);
+}
+MGAR_API int mgar_stem_conv3d_bf16_fwd_affine(const void *x, int N, int T, int H, int W, const float *w, float *w_packed,
+                                              const float *scale, const float *shift, int relu, void *y, void *stream) {
+    return stem_conv_impl<bf16_t, true>((const bf16_t *)x, N, T, H, W, w, w_packed, StemEpilogue{scale, shift, relu ? 1 : 0}, (bf16_t *)y, stream);
 }

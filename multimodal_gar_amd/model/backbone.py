@@ -79,6 +79,13 @@ class MaxPool3dSamePadding(nn.MaxPool3d):
         return y
 
 
+class _Like:
+    """shape and dtype of a tensor that does not exist (yet): what bn_ops._slice_stride reads of its second argument"""
+
+    def __init__(self, shape, dtype):
+        self.shape, self.dtype = torch.Size(shape), dtype
+
+
 class Unit3D(nn.Module):
     """Conv3d (no bias by default) + BatchNorm3d(eps=1e-3, momentum=0.01) + ReLU with dynamic
     'same' padding."""
@@ -107,12 +114,17 @@ class Unit3D(nn.Module):
 
     stem_kernel = True     # 3 -> 64, 7x7x7, stride 2 on the device: csrc/stem_conv.hip instead of pad + library convolution
 
+    def _stem_route(self, x):
+        """_stem_conv takes x (attributes of x and of the unit only: no tensor is touched)"""
+        c = self.conv3d
+        return bool(self.stem_kernel and x.is_cuda and x.dim() == 5 and x.dtype in (torch.float32, torch.bfloat16)
+                    and c.in_channels == 3 and c.out_channels == 64 and self._kernel_shape == (7, 7, 7) and self._stride == (2, 2, 2)
+                    and c.bias is None and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad)))
+
     def _stem_conv(self, x):
         """The I3D stem (Conv3d_1a_7x7) on csrc/stem_conv.hip: "same" padding inside the kernel, NCDHW in and out; or None."""
         c = self.conv3d
-        if not (self.stem_kernel and x.is_cuda and x.dim() == 5 and x.dtype in (torch.float32, torch.bfloat16)
-                and c.in_channels == 3 and c.out_channels == 64 and self._kernel_shape == (7, 7, 7) and self._stride == (2, 2, 2)
-                and c.bias is None and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad))):
+        if not self._stem_route(x):
             return None
         from .. import _lib as L
         if torch.is_autocast_enabled() and x.dtype == torch.float32:
@@ -129,16 +141,29 @@ class Unit3D(nn.Module):
     gemm_1x1 = os.environ.get("MGAR_I3D_GEMM_1X1", "1") != "0"        # 1x1x1 units on the device: library GEMMs (one per sample) instead of the library convolution
     wino_kernel = os.environ.get("MGAR_I3D_OWN_CONV", "1") != "0"     # 3x3x3, stride 1 on the device: csrc/conv3d_wino.hip (Winograd F(2,3) along W on the fp32 MFMA); bf16 payloads: csrc/conv3d_bf16.hip (direct, bf16 MFMA)
 
+    def _k3_bf16_route(self, x):
+        """_k3_conv_bf16 takes x (attributes only)"""
+        c = self.conv3d
+        return bool(self.wino_kernel and x.is_cuda and x.dim() == 5 and x.dtype == torch.bfloat16
+                    and self._kernel_shape == (3, 3, 3) and self._stride == (1, 1, 1) and c.bias is None and c.groups == 1
+                    and c.in_channels % 8 == 0 and x.shape[4] % 2 == 0 and x.is_contiguous()
+                    and c.weight.dtype in (torch.bfloat16, torch.float32)
+                    and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad)))
+
+    def _k3_route(self, x):
+        """the fp32 kernel of _k3_conv takes x (attributes only)"""
+        c = self.conv3d
+        return bool(self.wino_kernel and x.is_cuda and x.dim() == 5 and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+                    and self._kernel_shape == (3, 3, 3) and self._stride == (1, 1, 1) and c.bias is None and c.groups == 1
+                    and c.in_channels % 2 == 0 and x.shape[4] % 2 == 0 and x.is_contiguous() and c.weight.dtype == torch.float32
+                    and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad)))
+
     def _k3_conv_bf16(self, x):
         """bf16 payloads (the bf16 forward configurations, autocast on or off): csrc/conv3d_bf16.hip, a direct convolution on the
         bf16 MFMA, bf16 NCDHW in and out; the weight (bf16 as ForwardStep converts it, or fp32) goes in as fp32 and is rounded to
         bf16 when the kernel packs it, as in _stem_conv.  Or None."""
         c = self.conv3d
-        if not (self.wino_kernel and x.is_cuda and x.dim() == 5 and x.dtype == torch.bfloat16
-                and self._kernel_shape == (3, 3, 3) and self._stride == (1, 1, 1) and c.bias is None and c.groups == 1
-                and c.in_channels % 8 == 0 and x.shape[4] % 2 == 0 and x.is_contiguous()
-                and c.weight.dtype in (torch.bfloat16, torch.float32)
-                and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad))):
+        if not self._k3_bf16_route(x):
             return None
         from .. import _lib as L
         n, cin, d, h, w = x.shape
@@ -156,10 +181,7 @@ class Unit3D(nn.Module):
         c = self.conv3d
         if x.dtype == torch.bfloat16:
             return self._k3_conv_bf16(x)
-        if not (self.wino_kernel and x.is_cuda and x.dim() == 5 and x.dtype == torch.float32 and not torch.is_autocast_enabled()
-                and self._kernel_shape == (3, 3, 3) and self._stride == (1, 1, 1) and c.bias is None and c.groups == 1
-                and c.in_channels % 2 == 0 and x.shape[4] % 2 == 0 and x.is_contiguous() and c.weight.dtype == torch.float32
-                and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad))):
+        if not self._k3_route(x):
             return None
         from .. import _lib as L
         n, cin, d, h, w = x.shape
@@ -238,10 +260,80 @@ class Unit3D(nn.Module):
             return pool(self._bn_relu(z))
         return bn_ops.bn_apply_with_stats(pool.forward_valid(z), self.bn, True, stats, per_sample=self.per_sample_stats and z.shape[0] > 1)
 
+    # Eval mode: a BatchNorm with running statistics is a per-channel affine map, so it [+ the ReLU] goes into the store of the
+    # unit's own convolution kernel (the *_affine entry points of csrc/stem_conv.hip, conv3d_wino.hip, conv3d_bf16.hip): one launch
+    # per unit, the pre-BatchNorm tensor is never written, a bf16 payload is rounded once.  MGAR_I3D_FOLD_BN=0 (or this flag)
+    # restores convolution + bn_ops.bn_act (A/B in tests and profiles).
+    fold_bn_eval = os.environ.get("MGAR_I3D_FOLD_BN", "1") != "0"
+
+    def eval_fold_plan(self, x):
+        """Which *_affine entry point runs this unit on x in one launch: 'stem', 'k3' (fp32) or 'k3_bf16' -- or None for the
+        convolution + BatchNorm path.  Pure: reads attributes of x and of the unit, touches no tensor.  Folded when the switch is
+        on, the BatchNorm is in eval mode with running statistics, the activation is ReLU or none, nothing asks for a gradient
+        (input, convolution weight, BatchNorm affine parameters), the unit does not emit channels-last, and the unit's own
+        convolution kernel takes x (_stem_route / _k3_route / _k3_bf16_route); 1x1x1 units never are."""
+        if not (self.fold_bn_eval and self._use_batch_norm and (self._activation_fn is F.relu or self._activation_fn is None)
+                and not self.emit_channels_last):
+            return None
+        bn = self.bn
+        if bn.training or not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
+            return None
+        if torch.is_grad_enabled() and (x.requires_grad or self.conv3d.weight.requires_grad
+                                        or (bn.affine and (bn.weight.requires_grad or bn.bias.requires_grad))):
+            return None
+        if self._stem_route(x):
+            return 'stem'
+        if x.dtype == torch.bfloat16:
+            return 'k3_bf16' if self._k3_bf16_route(x) else None
+        return 'k3' if self._k3_route(x) else None
+
+    def _conv_folded(self, x, route, out):
+        """One call of the route's *_affine entry point: [relu](bn(conv(x))) with bn as sparse_ops.fold_bn's cached (scale, shift).
+        A 3x3x3 unit writes into ``out`` where that is a channel slice of a wider contiguous tensor (bn_ops._slice_stride) the
+        kernel's store can address (even batch stride; fp32: 8-byte aligned pairs); into a fresh tensor otherwise."""
+        from .. import _lib as L, bn_ops, sparse_ops
+        c = self.conv3d
+        scale, shift = sparse_ops.fold_bn(self.bn)
+        relu = int(self._activation_fn is F.relu)
+        if route == 'stem':
+            if torch.is_autocast_enabled() and x.dtype == torch.float32:
+                x = x.to(torch.get_autocast_dtype('cuda'))
+            x = x.contiguous()
+            n, _, t, h, w = x.shape
+            y = torch.empty((n, 64, (t + 1) // 2, (h + 1) // 2, (w + 1) // 2), dtype=x.dtype, device=x.device)
+            wp = torch.empty((L.raw("mgar_stem_conv3d_workspace_floats"),), dtype=torch.float32, device=x.device)
+            wf = c.weight.detach().float().contiguous()
+            name = "mgar_stem_conv3d_fwd_affine" if x.dtype == torch.float32 else "mgar_stem_conv3d_bf16_fwd_affine"
+            L.call(name, L.pptr(x, x.dtype), n, t, h, w, L.fptr(wf), L.fptr(wp), L.fptr(scale), L.fptr(shift), relu, L.pptr(y, x.dtype),
+                   L.stream_of(x))
+            return y
+        n, cin, d, h, w = x.shape
+        dt, cout = x.dtype, c.out_channels
+        bstride = bn_ops._slice_stride(out, _Like((n, cout, d, h, w), dt))
+        if bstride is not None and (bstride % 2 != 0 or out.data_ptr() % (8 if dt == torch.float32 else 2) != 0):
+            bstride = None
+        y = out if bstride is not None else torch.empty((n, cout, d, h, w), dtype=dt, device=x.device)
+        if bstride is None:
+            bstride = cout * d * h * w
+        if route == 'k3':
+            wp = torch.empty((L.raw("mgar_conv3d_k3_workspace_floats", cin, cout),), dtype=torch.float32, device=x.device)
+            wf = c.weight.detach().contiguous()
+            L.call("mgar_conv3d_k3_fwd_affine", L.fptr(x), n, cin, d, h, w, L.fptr(wf), cout, L.fptr(wp), L.fptr(scale), L.fptr(shift),
+                   relu, y.data_ptr(), bstride, L.stream_of(x))
+        else:
+            wp = torch.empty((L.raw("mgar_conv3d_k3_bf16_workspace_bytes", cin, cout),), dtype=torch.uint8, device=x.device)
+            wf = c.weight.detach().float().contiguous()
+            L.call("mgar_conv3d_k3_bf16_fwd_affine", L.pptr(x, torch.bfloat16), n, cin, d, h, w, L.fptr(wf), cout, wp.data_ptr(),
+                   L.fptr(scale), L.fptr(shift), relu, y.data_ptr(), bstride, L.stream_of(x))
+        return y
+
     def forward(self, x, out=None):
         """``out`` (optional): a channel slice y[:, c0:c1] of a wider tensor the result should land in (the caller's
-        concatenation); honoured where the fused BatchNorm + ReLU kernel writes the result, ignored otherwise --
-        the caller checks ``result is out``."""
+        concatenation); honoured where the fused BatchNorm + ReLU kernel (or, in eval mode, the convolution's own store) writes
+        the result, ignored otherwise -- the caller checks ``result is out``."""
+        route = self.eval_fold_plan(x)
+        if route is not None:
+            return self._conv_folded(x, route, out)
         return self._bn_relu(self._conv(x), out)
 
     def _bn_relu(self, x, out=None):
@@ -253,8 +345,9 @@ class Unit3D(nn.Module):
                 # as two kernels; I3D is frozen, so this is forward-only in MGAR-net)
                 from .. import bn_ops
                 relu_fused = self._activation_fn is F.relu
-                if self.per_sample_stats and x.shape[0] > 1:
-                    # several clips in one pass, each normalised with its own statistics = one pass per clip
+                if self.per_sample_stats and x.shape[0] > 1 and self.bn.training:
+                    # several clips in one pass, each normalised with its own statistics = one pass per clip (train mode only:
+                    # in eval mode every clip sees the same running statistics, the batch route below is already per clip)
                     y = bn_ops.bn_act_per_sample(x, self.bn, relu_fused, out=out, to_channels_last=self.emit_channels_last)
                     assert y is not None, "per_sample_stats is a forward-only (frozen backbone) device path"
                 else:
