@@ -720,8 +720,8 @@ int mgar_voxel_roi_pool_bwd(int M, int nsample, int C, const float *xyz, const f
  *   pooled_c = relu(max_s v)                               an empty neighbourhood (idx[m,0] < 0): f = 0, r = 0, v = pos_shift[c]
  *   z = sum_c w_out[j*C + c] * pooled_c                    fp32, an fmaf chain over ascending c
  *   o = fmaf(z, out_scale[j], out_shift[j]);   out[m*ld_out + j] = relu ? (o > 0 ? o : (o != o ? o : +0)) : o
- * A NaN is sticky in the running max and passes both ReLUs (torch.max / torch.relu); mgar_voxel_roi_pool_fwd drops a NaN in its
- * `>` / fmaxf and is unchanged.  out is ROW-major (M, ld_out): a column slice of a wider buffer is written in place, columns
+ * A NaN is sticky in the running max and passes both ReLUs (torch.max / torch.relu), as in mgar_voxel_roi_pool_fwd (whose arg
+ * is then the first NaN's slot).  out is ROW-major (M, ld_out): a column slice of a wider buffer is written in place, columns
  * j >= Co of a row are not touched.  No arg-max, no atomics, no cross-row state: a row's bits depend on its idx row, the rows it
  * names and the parameters only -- not on M, its position or its workgroup neighbours.  w_pos (C, 3), w_out (Co, C), the four
  * vectors fp32 and required.  1 <= C, Co <= 32 (above: MGAR_EUNSUPPORTED), 1 <= nsample <= 255, ld_f >= C, ld_out >= Co; a bad

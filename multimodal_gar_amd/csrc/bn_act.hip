@@ -38,11 +38,7 @@ __device__ __forceinline__ float block_sum(float v, float *scratch) {
     return t;
 }
 
-// ReLU and the max scan PROPAGATE NaN as torch.relu / torch.max do (fmaxf(NaN, 0) is 0 and NaN > best is false: a diverged
-// channel would come out as zeros).  Compare-selects: a NaN fails every comparison.
-__device__ __forceinline__ float relu_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
-// true when a replaces best in a running maximum: a > best, or a is the first NaN
-__device__ __forceinline__ bool max_takes(float a, float best) { return !(a <= best) && best == best; }
+// ReLU and the max scan PROPAGATE NaN as torch.relu / torch.max do: relu_nan / max_takes of common.hpp.
 
 // element e of channel c (0 <= e < B*P) lives at ((e / P) * C + c) * P + e % P
 __device__ __forceinline__ size_t chan_off(long long e, int c, int C, int P) {

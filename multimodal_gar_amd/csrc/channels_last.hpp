@@ -84,7 +84,7 @@ __global__ __launch_bounds__(CL_THREADS) void bn_cl_apply_kernel(const T *__rest
         float4 v = Payload<T>::ld4(x + row * C + c);
         v.x = (v.x - mu.x) * (is.x * g.x) + b.x; v.y = (v.y - mu.y) * (is.y * g.y) + b.y;
         v.z = (v.z - mu.z) * (is.z * g.z) + b.z; v.w = (v.w - mu.w) * (is.w * g.w) + b.w;
-        if (RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (RELU) { v.x = relu_nan(v.x); v.y = relu_nan(v.y); v.z = relu_nan(v.z); v.w = relu_nan(v.w); }
         Payload<T>::st4(y + row * ldy + c, v);
     }
 }
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(CL_THREADS) void bn_to_cl_apply_kernel(const T *__r
         if (c < C && p < R) {
             const int si = (per_sample ? s * C : 0) + c;
             v = (Payload<T>::ld(x + ((size_t)s * C + c) * R + p) - mean[si]) * (invstd[si] * (gamma ? gamma[c] : 1.f)) + (beta ? beta[c] : 0.f);
-            if (RELU) v = fmaxf(v, 0.f);
+            if (RELU) v = relu_nan(v);
         }
         tile[pl][cl] = v;
     }
@@ -133,14 +133,14 @@ __global__ __launch_bounds__(CL_THREADS) void maxpool3d_cl_kernel(const T *__res
         const int t0 = to * g.st - g.pt, h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
         const int t1 = t0 + g.kt, h1 = h0 + g.kh, w1 = w0 + g.kw;
         const bool pad = t0 < 0 || h0 < 0 || w0 < 0 || t1 > g.T || h1 > g.H || w1 > g.W;
-        const float init = pad ? 0.f : -__builtin_inff();             // the zero padding takes part in the max
+        const float init = pad ? 0.f : -__builtin_inff();             // the zero padding takes part in the max; a NaN in the window wins (torch.max_pool3d)
         float4 best = make_float4(init, init, init, init);
         const T *base = x + (size_t)n * g.T * g.H * g.W * g.C + c;
         for (int t = max(t0, 0); t < min(t1, g.T); ++t)
             for (int h = max(h0, 0); h < min(h1, g.H); ++h)
                 for (int w = max(w0, 0); w < min(w1, g.W); ++w) {
                     const float4 v = Payload<T>::ld4(base + (((size_t)t * g.H + h) * g.W + w) * g.C);
-                    best.x = fmaxf(best.x, v.x); best.y = fmaxf(best.y, v.y); best.z = fmaxf(best.z, v.z); best.w = fmaxf(best.w, v.w);
+                    best.x = max_nan(best.x, v.x); best.y = max_nan(best.y, v.y); best.z = max_nan(best.z, v.z); best.w = max_nan(best.w, v.w);
                 }
         Payload<T>::st4(y + (((size_t)(n * g.To + to) * g.Ho + ho) * g.Wo + wo) * g.C + c, best);
     }

@@ -66,6 +66,15 @@ __device__ __forceinline__ float conv_affine(float acc, float scale, float shift
     return relu ? (v > 0.f ? v : (v != v ? v : 0.f)) : v;
 }
 
+// ReLU and running maxima PROPAGATE NaN as torch.relu / torch.max / torch.max_pool3d do (fmaxf(NaN, 0) is 0 and NaN > best is
+// false: a diverged channel would come out as zeros and training would go on with a finite loss).  Compare-selects: a NaN
+// fails every comparison.  On finite operands they return what fmaxf returns (the sign of a zero that meets a zero of the
+// other sign aside: the running value is kept, and relu_nan(-0) is +0).
+__device__ __forceinline__ float relu_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
+// true when a replaces best in a running maximum: a > best, or a is the first NaN
+__device__ __forceinline__ bool max_takes(float a, float best) { return !(a <= best) && best == best; }
+__device__ __forceinline__ float max_nan(float best, float a) { return max_takes(a, best) ? a : best; }
+
 void set_error(const char *msg);
 
 // ---- optional per-kernel timing (bench.py's roofline table) --------------------------------------

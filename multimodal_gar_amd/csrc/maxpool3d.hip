@@ -13,6 +13,8 @@
 // with the last three 2-D pooled quads in registers (see maxpool3d_same_vec_kernel); per input row it
 // loads one aligned 16-byte vector (two for stride 2) plus the one or two edge elements and forms the four
 // horizontal maxima in registers.  A one-thread-per-output kernel covers the other geometries.
+// A NaN anywhere in a window is the window's maximum, as in torch.max_pool3d: every maximum is max_nan (common.hpp), also
+// against the -inf edge sentinels, and the zero padding joins through relu_nan.
 #include "common.hpp"
 #include "payload.hpp"
 
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(256) void maxpool3d_same_kernel(const T *__restrict
         for (int t = max(t0, 0); t < min(t1, g.T); ++t)
             for (int h = max(h0, 0); h < min(h1, g.H); ++h) {
                 const T *row = base + ((size_t)t * g.H + h) * g.W;
-                for (int w = max(w0, 0); w < min(w1, g.W); ++w) best = fmaxf(best, Payload<T>::ld(row + w));
+                for (int w = max(w0, 0); w < min(w1, g.W); ++w) best = max_nan(best, Payload<T>::ld(row + w));
             }
         Payload<T>::st(y + e, best);
     }
@@ -79,18 +81,18 @@ __global__ __launch_bounds__(256) void maxpool3d_same_vec_kernel(const T *__rest
                 const float4 v = Payload<T>::ld4(row);
                 const float lft = wb > 0 ? Payload<T>::ld(row - 1) : ninf;
                 const float rgt = wb + 4 < g.W ? Payload<T>::ld(row + 4) : ninf;
-                b0 = fmaxf(b0, fmaxf(fmaxf(lft, v.x), v.y));
-                b1 = fmaxf(b1, fmaxf(fmaxf(v.x, v.y), v.z));
-                b2 = fmaxf(b2, fmaxf(fmaxf(v.y, v.z), v.w));
-                b3 = fmaxf(b3, fmaxf(fmaxf(v.z, v.w), rgt));
+                b0 = max_nan(b0, max_nan(max_nan(lft, v.x), v.y));
+                b1 = max_nan(b1, max_nan(max_nan(v.x, v.y), v.z));
+                b2 = max_nan(b2, max_nan(max_nan(v.y, v.z), v.w));
+                b3 = max_nan(b3, max_nan(max_nan(v.z, v.w), rgt));
             } else {        // outputs j cover inputs wb + 2j .. wb + 2j + 2
                 const float4 v = Payload<T>::ld4(row);
                 const float4 u = Payload<T>::ld4(row + 4);
                 const float rgt = wb + 8 < g.W ? Payload<T>::ld(row + 8) : ninf;
-                b0 = fmaxf(b0, fmaxf(fmaxf(v.x, v.y), v.z));
-                b1 = fmaxf(b1, fmaxf(fmaxf(v.z, v.w), u.x));
-                b2 = fmaxf(b2, fmaxf(fmaxf(u.x, u.y), u.z));
-                b3 = fmaxf(b3, fmaxf(fmaxf(u.z, u.w), rgt));
+                b0 = max_nan(b0, max_nan(max_nan(v.x, v.y), v.z));
+                b1 = max_nan(b1, max_nan(max_nan(v.z, v.w), u.x));
+                b2 = max_nan(b2, max_nan(max_nan(u.x, u.y), u.z));
+                b3 = max_nan(b3, max_nan(max_nan(u.z, u.w), rgt));
             }
         }
         p2 = make_float4(b0, b1, b2, b3);
@@ -100,13 +102,13 @@ __global__ __launch_bounds__(256) void maxpool3d_same_vec_kernel(const T *__rest
             if (min(t1, g.T) - 1 != t) break;
             const int lo = max(t0, 0);                     // window = slices lo .. t  (at most 3)
             float4 r = p2;
-            if (lo <= t - 1) { r.x = fmaxf(r.x, p1.x); r.y = fmaxf(r.y, p1.y); r.z = fmaxf(r.z, p1.z); r.w = fmaxf(r.w, p1.w); }
-            if (lo <= t - 2) { r.x = fmaxf(r.x, p0.x); r.y = fmaxf(r.y, p0.y); r.z = fmaxf(r.z, p0.z); r.w = fmaxf(r.w, p0.w); }
+            if (lo <= t - 1) { r.x = max_nan(r.x, p1.x); r.y = max_nan(r.y, p1.y); r.z = max_nan(r.z, p1.z); r.w = max_nan(r.w, p1.w); }
+            if (lo <= t - 2) { r.x = max_nan(r.x, p0.x); r.y = max_nan(r.y, p0.y); r.z = max_nan(r.z, p0.z); r.w = max_nan(r.w, p0.w); }
             const bool pad = pad_h || t0 < 0 || t1 > g.T;  // zero padding takes part in the max wherever the window leaves the input
             if (g.pad_zero) {
-                if (pad || pad_l) r.x = fmaxf(r.x, 0.f);
-                if (pad) { r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); }
-                if (pad || pad_r) r.w = fmaxf(r.w, 0.f);
+                if (pad || pad_l) r.x = relu_nan(r.x);
+                if (pad) { r.y = relu_nan(r.y); r.z = relu_nan(r.z); }
+                if (pad || pad_r) r.w = relu_nan(r.w);
             }
             Payload<T>::st4(y + ((nc * g.To + to) * g.Ho + ho) * g.Wo + wq * 4, r);
             ++to;

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void pointwise_dw_kernel(const float *__restri
                     } else {
                         const float sc = act_sc[r], sh = act_sh[r], mu = act_mu[r];
                         v.x = (v.x - mu) * sc + sh; v.y = (v.y - mu) * sc + sh; v.z = (v.z - mu) * sc + sh; v.w = (v.w - mu) * sc + sh;
-                        if (act.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                        if (act.relu) { v.x = relu_nan(v.x); v.y = relu_nan(v.y); v.z = relu_nan(v.z); v.w = relu_nan(v.w); }
                     }
                 }
                 float *d = lds + row * DW_LD + c4;
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void pointwise_dw_kernel(const float *__restri
                             v = pair_of(v, row - OB * 32, chv >= Cin);
                         } else {
                             v = (v - act_mu[row - OB * 32]) * act_sc[row - OB * 32] + act_sh[row - OB * 32];
-                            if (act.relu) v = fmaxf(v, 0.f);
+                            if (act.relu) v = relu_nan(v);
                         }
                     }
                 }

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_fwd_kernel(PfArgs<T> a) {
                 const float4 ac = *reinterpret_cast<const float4 *>(act + 4 * ch);
                 const float sc = ac.x, sh = ac.y, mu = ac.z;
                 v.x = (v.x - mu) * sc + sh; v.y = (v.y - mu) * sc + sh; v.z = (v.z - mu) * sc + sh; v.w = (v.w - mu) * sc + sh;
-                if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                if (relu) { v.x = relu_nan(v.x); v.y = relu_nan(v.y); v.z = relu_nan(v.z); v.w = relu_nan(v.w); }
                 if (ch >= a.Cin) v = make_float4(0.f, 0.f, 0.f, 0.f);   // padding channels stay zero (W is zero there too)
             }
 #pragma unroll

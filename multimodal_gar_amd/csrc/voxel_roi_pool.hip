@@ -144,10 +144,10 @@ __global__ __launch_bounds__(VP_THREADS) void vrp_fwd_kernel(int M, int nsample,
                 const float p = w0 * rx + w1 * ry + w2 * rz;
                 const float f = live ? Payload<T>::ld(feats + (size_t)j * ld_f + c) : 0.f;
                 const float v = f + ((p - mu) * sc + sh);
-                if (v > best) { best = v; bi = s; }
+                if (max_takes(v, best)) { best = v; bi = s; }   // a NaN row wins, as torch.max
             }
         }
-        tile[q][c] = fmaxf(best, 0.f);
+        tile[q][c] = relu_nan(best);
         targ[q][c] = (unsigned char)bi;
     }
     __syncthreads();
@@ -167,8 +167,6 @@ __global__ __launch_bounds__(VP_THREADS) void vrp_fwd_kernel(int M, int nsample,
 // conflict).  Phase 2: lane j of the half-wave holds row j of w_out in registers and reads the query's pooled row as
 // broadcast 16-byte LDS reads -- an fmaf chain over ascending c, then the affine [+ ReLU] store of the *_affine sparse-conv
 // entries, Co contiguous elements per half-wave into the row-major (M, ld_out) result.  No arg-max, no transpose.
-__device__ __forceinline__ float relu_nan(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
-
 template <typename T>
 __global__ __launch_bounds__(VP_THREADS) void vrp_eval_kernel(int M, int nsample, int C, int Co, const float *__restrict__ xyz,
                                                               const float *__restrict__ new_xyz, const T *__restrict__ feats,

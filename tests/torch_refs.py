@@ -546,3 +546,81 @@ def bn_from_partials_bounds(cnt, mean_k, m2_k, eps, group=256, direct_max=1024):
         cnt, mean_k, m2_k = np.array(gc), np.stack(gm, 1), np.stack(gq, 1)
         dd += U32
     return bn_merge_bounds(cnt, mean_k, m2_k, dd * np.abs(mean_k) + TINY32, dd * m2_k + TINY32, eps)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Channels-last / row-major BatchNorm (csrc/channels_last.hpp) and 3-D max pooling (csrc/maxpool3d.hip).
+CL_THREADS = 256
+
+
+def bn_cl_chunk_rows(S, R):
+    """Rows per statistics chunk: cl_chunk_rows() of channels_last.hpp restated (at least 256 rows, about 2 048 workgroups
+    in all, never more than R).  Statistics over all samples call it as (1, S * R)."""
+    return int(min(max(-(-(S * R) // 2048), 256), R))
+
+
+def bn_cl_partial_stats_bounds(xr, chunk):
+    """What bn_cl_partial_kernel leaves per (channel, chunk) of the rows xr (R, C) float64 of one statistics group, and how far
+    off it may be: (cnt (K), mean_k, M2_k, dmean_k, dM2_k (C, K)), the format of bn_partial_stats_bounds.  Per chunk of nk rows,
+    with p = the chunk's FIRST row (the pivot, an input value: exact, dp = 0), rpar = 256 // (C / 4) row lanes, L = ceil(nk /
+    rpar) additions per lane and rpar - 1 more when the lanes are added in order:
+      s = sum (x - p): x - p (1 rounding) and at most L + rpar - 1 additions:  |ds| <= gamma_u(L + rpar) * A1,  A1 = sum |x - p|;
+      q = sum (x - p)^2: two more roundings per term:                          |dq| <= gamma_u(L + rpar + 2) * A2,  A2 = sum (x - p)^2;
+      chunk mean = p + s / nk in double, rounded once:  dmean = |ds| / nk + u |mean_k|;
+      M2 = q - s^2 / nk in double, rounded once:  dM2 = |dq| + (2 |s| |ds| + ds^2) / nk + u M2,  |s| = nk |mean_k - p|."""
+    xr = np.asarray(xr, np.float64)
+    rows, C = xr.shape
+    rpar = CL_THREADS // (C // 4)
+    out = []
+    for r0 in range(0, rows, chunk):
+        v = xr[r0:r0 + chunk]
+        nk = v.shape[0]
+        p = v[0]
+        L = -(-nk // rpar)
+        dev_ = np.abs(v - p)
+        a1, a2 = dev_.sum(0), (dev_ ** 2).sum(0)
+        mean_k = v.mean(0)
+        m2_k = ((v - mean_k) ** 2).sum(0)
+        ds = gamma_u(L + rpar) * a1
+        s_abs = nk * np.abs(mean_k - p)
+        dmean = ds / nk + U32 * np.abs(mean_k) + TINY32
+        dm2 = gamma_u(L + rpar + 2) * a2 + (2.0 * s_abs * ds + ds * ds) / nk + U32 * m2_k + TINY32
+        out.append((float(nk), mean_k, m2_k, dmean, dm2))
+    cnt = np.array([o[0] for o in out])
+    return (cnt,) + tuple(np.stack([o[i] for o in out], 1) for i in (1, 2, 3, 4))
+
+
+def bn_cl_train_stats_bounds(x, per_sample, eps):
+    """mgar_bn_cl_train_stats on x (S, R, C): float64 (mean, var, mean bound, invstd bound, var bound), each (C), or (S * C)
+    with per-sample statistics (sample-major, as the entry point writes them)."""
+    x = np.asarray(x, np.float64)
+    S, Rr, C = x.shape
+    if per_sample:
+        chunk = bn_cl_chunk_rows(S, Rr)
+        parts = [bn_merge_bounds(*bn_cl_partial_stats_bounds(x[s], chunk), eps) for s in range(S)]
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(5))
+    return bn_merge_bounds(*bn_cl_partial_stats_bounds(x.reshape(S * Rr, C), bn_cl_chunk_rows(1, S * Rr)), eps)
+
+
+def bn_rows_bwd_lane_chain(rows, C):
+    """The longest chain of additions of bn_rows_bwd_partial_kernel: a row lane's ceil(chunk / rpar), then the rpar lanes in
+    order (the argument of bn_bwd_bounds)."""
+    rpar = CL_THREADS // (C // 4)
+    return -(-bn_cl_chunk_rows(1, rows) // rpar) + rpar - 1
+
+
+def same_pads(size, k, s):
+    """(front, back) zero padding of one axis of the reference's MaxPool3dSamePadding (model/backbone.py compute_pad)."""
+    total = max(k - s, 0) if size % s == 0 else max(k - size % s, 0)
+    return total // 2, total - total // 2
+
+
+def maxpool3d_ref(x, k, s, pad_value):
+    """x (..., T, H, W) -> (..., ceil(T / st), ceil(H / sh), ceil(W / sw)) float64: pad every axis by same_pads with
+    pad_value (0: the zero padding takes part, "same"; -inf: only the input's own elements count, "valid"), then the maximum
+    of every k window at stride s.  A NaN in a window is its maximum (np.max, as torch.max_pool3d).  Exact: no bound."""
+    x = np.asarray(x, np.float64)
+    pads = [same_pads(x.shape[-3 + i], k[i], s[i]) for i in range(3)]
+    xp = np.pad(x, [(0, 0)] * (x.ndim - 3) + pads, constant_values=pad_value)
+    win = np.lib.stride_tricks.sliding_window_view(xp, tuple(k), axis=(-3, -2, -1))
+    return win[..., ::s[0], ::s[1], ::s[2], :, :, :].max(axis=(-3, -2, -1))
