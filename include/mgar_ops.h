@@ -31,7 +31,7 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
-#define MGAR_ABI_VERSION 20   /* bumped on any signature change; mgar_abi_version() returns it */
+#define MGAR_ABI_VERSION 21  /* bumped on any signature change; mgar_abi_version() returns it */
 
 /* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
@@ -503,6 +503,22 @@ int mgar_pointwise_conv_dw_maxgrad(const float *x, const float *x4, int B, int C
                                    const float *gamma, const float *coef, const unsigned char *arg, const float *dmask,
                                    float *workspace, float *dw, void *stream);
 
+/* Inference tail of a shared MLP, [BatchNorm -> ReLU ->] conv 1x1 -> BatchNorm(running statistics) [-> ReLU] -> max over
+ * nsample, in one launch that never writes the conv's output (B, Cout, M, nsample) (ABI 21; forward only):
+ *   z[b,o,m,s]     = sum_i w[o*w_row_stride + i*w_col_stride] * act_i(x[b,i,m,s])      act_i as in mgar_pointwise_conv_fwd
+ *   pooled[b,o,m]  = max_s relu?(fmaf(z[b,o,m,s], out_scale[o], out_shift[o]))
+ * x (B, Cin, M, nsample), pooled (B, Cout, M); (out_scale, out_shift) = the eval-mode BatchNorm of the conv's output as an
+ * affine map (Cout floats each).  in_mean NULL = identity prologue; in_gamma / in_beta NULL = 1 / 0.  ReLU and max propagate
+ * a NaN (a NaN in a group makes that group's outputs NaN and no other's); a ReLU result is never -0.
+ * Needs nsample in {4, 8, 16, 32, 64, 128}, 1 <= Cin <= 256, Cout <= 64 (MGAR_EUNSUPPORTED otherwise); B * M == 0 is
+ * MGAR_OK and writes nothing.  mgar_pointwise_conv_maxpool_eval_bf16_fwd: x and pooled address bf16 elements (every vector
+ * and w fp32, fp32 accumulation), pooled rounded once, after the max; it is called by name, not as a `_bf16` payload twin. */
+int mgar_pointwise_conv_maxpool_eval_fwd(const float *x, int B, int Cin, int M, int nsample, const float *w,
+                                         int w_row_stride, int w_col_stride, int Cout, const float *in_mean,
+                                         const float *in_invstd, const float *in_gamma, const float *in_beta, int in_relu,
+                                         const float *out_scale, const float *out_shift, int out_relu, float *pooled,
+                                         void *stream);
+
 /* MaxPool3dSamePadding.forward of the reference's I3D (model/backbone.py:99-131): zero "same"
  * padding + max pooling without materialising the padded tensor.  x (NC, T, H, W) -> y (NC, ceil(T/st),
  * ceil(H/sh), ceil(W/sw)).  Forward only (I3D is frozen in MGAR-net). */
@@ -966,6 +982,12 @@ int mgar_voxel_roi_pool_eval_bf16_fwd(int M, int nsample, int C, int Co, const f
                                       const float *pos_scale, const float *pos_shift, const float *w_out,
                                       const float *out_scale, const float *out_shift, int relu, void *out, int ld_out,
                                       void *stream);
+/* x, pooled (every parameter vector and w fp32) */
+int mgar_pointwise_conv_maxpool_eval_bf16_fwd(const void *x, int B, int Cin, int M, int nsample, const float *w,
+                                              int w_row_stride, int w_col_stride, int Cout, const float *in_mean,
+                                              const float *in_invstd, const float *in_gamma, const float *in_beta,
+                                              int in_relu, const float *out_scale, const float *out_shift, int out_relu,
+                                              void *pooled, void *stream);
 
 #ifdef __cplusplus
 }

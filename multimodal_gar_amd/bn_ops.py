@@ -2,6 +2,8 @@
 csrc/bn_act.hip -- the tail of every [Conv 1x1 -> BatchNorm -> ReLU] block of the shared MLPs
 (reference pointnet2_batch/pointnet2_modules.py:37-45 and friends).  Parameters and running
 statistics live in the caller's ``nn.BatchNormNd`` module, so state dicts are unchanged."""
+import os
+
 import torch
 import torch.nn as nn
 from torch.autograd import Function
@@ -370,9 +372,107 @@ FUSED_CONV_MAX_CHANNELS = 64   # csrc/pointwise_fwd.hip: Cout <= 64 in both dire
 FUSED_STATS_MAX_CHANNELS = 32   # csrc/pointwise_fwd.hip: the statistics epilogue exists for Cout <= 32
 
 
-def bn_act_conv(x, bn, relu, conv, rowmajor_grad=False, in_stats=None, want_out_stats=False):
+# Inference (every BatchNorm on running statistics, no gradient) keeps the shared MLPs on csrc/pointwise_fwd.hip: a hidden
+# [BN -> ReLU -> conv] step is mgar_pointwise_conv_fwd with the running statistics, and the tail [BN -> ReLU ->] conv -> BN
+# [-> ReLU] -> max over nsample is ONE launch of mgar_pointwise_conv_maxpool_eval_fwd / _bf16_fwd, which never writes the
+# conv's output.  MGAR_MLP_EVAL_FUSE=0 (or this flag) restores bn_act + library GEMM + bn_act_maxpool (A/B in tests, profiles).
+MLP_EVAL_FUSE = os.environ.get("MGAR_MLP_EVAL_FUSE", "1") != "0"
+EVAL_POOL_NSAMPLES = (4, 8, 16, 32, 64, 128)   # csrc/pointwise_fwd.hip MAXPOOL epilogue: groups lane-aligned in a 128-column tile
+EVAL_POOL_MAX_IN = 256                         # mgar_pointwise_conv_maxpool_eval_fwd: 1 <= Cin <= 256, Cout <= 64
+EVAL_MIN_COLUMNS = 1 << 16                     # the threshold of every fused kernel of this file
+
+
+def eval_mlp_plan(x, bn, conv, bn2=None, others=()):
+    """Which inference kernel takes conv(relu?(bn(x))) -- "conv" -- or, with ``bn2``, max over the last axis of
+    relu?(bn2(conv(relu?(bn(x))))) -- "conv_maxpool"; None = neither (the caller keeps its other route).  ``bn`` None: the conv
+    reads x itself.  ``others``: further modules the fused step swallows (the ReLUs).  Decided from attributes alone -- no tensor
+    is read, nothing synchronises: the switch is on; x is a device tensor, fp32 or bf16; every BatchNorm is in eval mode with
+    running statistics; the conv is point-wise and bias-free; no gradient is required (grad mode off, or neither x nor a
+    parameter of these layers requires one); no forward (pre-)hook sits on these layers; B * P >= 65 536 columns; and the shapes
+    are the kernels': "conv" C, Cout <= 64 and P % 4 == 0, "conv_maxpool" x (B, C, M, ns) with ns in {4, .., 128}, C <= 256,
+    Cout <= 64."""
+    from .nn_utils import _BN_TYPES, _is_pointwise
+    if not (MLP_EVAL_FUSE and x.is_cuda and x.dtype in _PAYLOADS and x.dim() >= 3):
+        return None
+    mods = [m for m in (bn, conv, bn2) + tuple(others) if m is not None]
+    for m in (bn, bn2):
+        if m is not None and not (isinstance(m, _BN_TYPES) and not m.training and m.track_running_stats
+                                  and m.running_mean is not None and m.running_var is not None):
+            return None
+    if not _is_pointwise(conv) or conv.bias is not None:
+        return None
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in mods for p in m.parameters(recurse=False))):
+        return None
+    if any(m._forward_hooks or m._forward_pre_hooks for m in mods):
+        return None
+    c, cout = x.shape[1], conv.out_channels
+    if conv.in_channels != c or c < 1 or (bn is not None and bn.num_features != c) or (bn2 is not None and bn2.num_features != cout):
+        return None
+    columns = x.shape[0]
+    for s in x.shape[2:]:
+        columns *= s
+    if columns < EVAL_MIN_COLUMNS:
+        return None
+    if bn2 is not None:
+        ok = x.dim() == 4 and x.shape[3] in EVAL_POOL_NSAMPLES and c <= EVAL_POOL_MAX_IN and cout <= FUSED_CONV_MAX_CHANNELS
+        return "conv_maxpool" if ok else None
+    if bn is None or c > FUSED_CONV_MAX_CHANNELS or cout > FUSED_CONV_MAX_CHANNELS or (columns // x.shape[0]) % 4 != 0:
+        return None
+    return "conv"
+
+
+def bn_act_conv_maxpool_eval(x, bn, relu, conv, bn2, relu2, others=()):
+    """Inference: max over the last axis of relu2?(bn2(conv(relu?(bn(x))))) for x (B, C, M, ns) -> (B, Ck, M) as one launch
+    (csrc/pointwise_fwd.hip, MAXPOOL epilogue), or None where eval_mlp_plan refuses.  ``bn`` None: conv(x) with no prologue (an
+    MLP whose only conv is its first layer).  bn2 enters as the float64-folded (scale, shift) of sparse_ops.fold_bn, cached
+    on the module."""
+    if eval_mlp_plan(x, bn, conv, bn2, others) != "conv_maxpool":
+        return None
+    from .sparse_ops import fold_bn
+    b, c, m, ns = x.shape
+    ck = conv.out_channels
+    dt = x.dtype
+    x4 = x.contiguous()
+    w = _f32(conv.weight.detach()).reshape(ck, c).contiguous()
+    scale, shift = fold_bn(bn2)
+    mean = invstd = gamma = beta = None
+    if bn is not None:
+        mean, invstd = _stats(x4, bn)
+        gamma, beta = _affine(bn, c, x.device)
+        gamma, beta = gamma.detach(), beta.detach()
+    out = torch.empty((b, ck, m), dtype=dt, device=x.device)
+    L.call("mgar_pointwise_conv_maxpool_eval_fwd" if dt == torch.float32 else "mgar_pointwise_conv_maxpool_eval_bf16_fwd",
+           L.pptr(x4, dt), b, c, m, ns, L.fptr(w), c, 1, ck, L.fptr(mean), L.fptr(invstd), L.fptr(gamma), L.fptr(beta), int(relu),
+           L.fptr(scale), L.fptr(shift), int(relu2), L.pptr(out, dt), L.stream_of(x4))
+    return out
+
+
+def _bn_act_conv_eval(x, bn, relu, conv, others):
+    """Inference [BN -> ReLU -> conv] on mgar_pointwise_conv_fwd with the running statistics: no statistics epilogue, no
+    autograd node."""
+    if eval_mlp_plan(x, bn, conv, None, others) != "conv":
+        return None
+    c, cout = x.shape[1], conv.out_channels
+    x3 = x.contiguous().flatten(2)
+    b, _, p = x3.shape
+    dt = x3.dtype
+    mean, invstd = _stats(x3, bn)
+    gamma, beta = _affine(bn, c, x.device)
+    gamma, beta = gamma.detach(), beta.detach()
+    w = _f32(conv.weight.detach()).reshape(cout, c).contiguous()
+    y = torch.empty((b, cout, p), dtype=dt, device=x.device)
+    L.payload_call("mgar_pointwise_conv_fwd", dt, L.pptr(x3, dt), b, c, p, L.fptr(w), c, 1, cout, L.fptr(mean), L.fptr(invstd),
+                   L.fptr(gamma), L.fptr(beta), int(relu), L.pptr(y, dt), L.stream_of(x3))
+    return y.view(x.shape[0], cout, *x.shape[2:])
+
+
+def bn_act_conv(x, bn, relu, conv, rowmajor_grad=False, in_stats=None, want_out_stats=False, others=(), eval_steps=True):
     """conv(relu?(bn(x))) for a bias-free kernel-size-1 ``conv`` in one fused step, or None if the
-    shapes are outside the fused kernel (the caller then runs bn_act and the GEMM separately)."""
+    shapes are outside the fused kernel (the caller then runs bn_act and the GEMM separately).  ``others``, ``eval_steps``: the
+    further modules of the step and the caller's consent to the inference form (eval_mlp_plan)."""
+    if not bn.training:   # inference: the same kernel on the running statistics (eval_mlp_plan), else the caller's route
+        y = _bn_act_conv_eval(x, bn, relu, conv, others) if eval_steps else None
+        return y if y is None or not want_out_stats else (y, None)
     if not (x.is_cuda and x.dtype in _PAYLOADS and bn.training and x.dim() >= 3 and conv.bias is None):
         return None
     if x.dtype != torch.float32 and torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):

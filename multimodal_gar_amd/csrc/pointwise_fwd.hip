@@ -30,6 +30,12 @@
 // so the kernel reads the PRE-BN tensor x4 (B, C, M, ns) where it would read a dense dx, plus one arg byte and one d float per
 // float4 (ns % 4 == 0: the four columns of a float4 lie in one group), and forms dx while feeding the MFMA, in the operation
 // order of bn_max_bwd_apply_kernel: the products are bit for bit those of the dense route, and dx is never written or re-read.
+//
+// MAXPOOL epilogue (inference: the layer's output (B, Cout, M, ns) is followed by a running-statistics BatchNorm [+ ReLU] and the
+// max over ns): at tile finish a lane holds four consecutive columns of a row, so with ns % 4 == 0 and 128 % ns == 0 a group is
+// the four components of ns / 4 neighbouring lanes of one half-wave.  The epilogue forms relu?(fmaf(acc, scale_o, shift_o)),
+// takes the NaN-propagating max over the components and over the group's lanes (xor shuffles inside the half-wave) and the
+// group's first lane stores pooled[b, o, p / ns]: the (B, Cout, M, ns) tensor is never written.
 #include <type_traits>
 
 #include "common.hpp"
@@ -44,6 +50,11 @@ constexpr int PF_COLS = 128;  // columns per wave tile
 // registers + two slab buffers stay under 256 VGPRs (2 waves per SIMD instead of 1)
 // (4 for its GRAD instance, whose slabs also carry the groups' (d, arg): 8 spilled)
 template <int OB, bool GRAD = false> struct PfSlab { static constexpr int KC = OB == 1 ? 16 : (GRAD ? 4 : 8); };
+
+struct PfPool {                 // MAXPOOL epilogue: y = pooled (B, Cout, P / ns)
+    const float *scale, *shift; // (Cout) eval-mode BatchNorm of the layer's output as an affine map
+    int ns, relu;
+};
 
 struct PfGrad {                 // GRAD operand mode: x = x4 (B, Cin, M, ns), P = M * ns
     const unsigned char *arg;   // (B, Cin, M) arg-max slot of every group
@@ -66,21 +77,27 @@ struct PfArgs {
     // sample -- so that the BatchNorm that follows needs no pass over y for its statistics (csrc/bn_act.hip, bn_finalize_kernel)
     float *stats;
     PfGrad g;        // GRAD instances only (mean / invstd / gamma are then those of the max-pool layer's BatchNorm)
+    PfPool mp;       // MAXPOOL instances only
 };
 
 // one slab of operand registers; the GRAD instances carry the group's (d, arg) next to every float4 and the float4's first slot
 template <int KS, bool GRAD> struct PfBuf { float4 v[KS]; };
 template <int KS> struct PfBuf<KS, true> { float4 v[KS]; float d[KS]; int a[KS]; int s0; };
 
-template <int OB, typename T, bool STATS = false, bool GRAD = false>
+template <int OB, typename T, bool STATS = false, bool GRAD = false, bool MAXPOOL = false>
 __global__ __launch_bounds__(256, 2) void pointwise_fwd_kernel(PfArgs<T> a) {
     constexpr int PF_KC = PfSlab<OB, GRAD>::KC, KS = PF_KC / 2;
     constexpr int WLD = OB == 1 ? 32 : 96;  // LDS row stride of W: the two half-waves hit disjoint banks
     extern __shared__ float lds[];          // [nkc*16][WLD] weights, then [nkc*16][4] (sc, sh, mu, -); GRAD: (k, m0, mu, is), then [nkc*16] m1
+                                            // MAXPOOL: then [OB*32][2] (scale, shift) of the output rows
     const int nkc = (a.Cin + PF_KC - 1) / PF_KC;
     float *wl = lds;
     float *act = lds + (size_t)nkc * PF_KC * WLD;
     float *gm1 = act + (size_t)nkc * PF_KC * 4;
+    if constexpr (MAXPOOL) {
+        for (int o = threadIdx.x; o < OB * 32; o += 256)
+            *reinterpret_cast<float2 *>(gm1 + 2 * o) = o < a.Cout ? make_float2(a.mp.scale[o], a.mp.shift[o]) : make_float2(0.f, 0.f);
+    }
     for (int e = threadIdx.x; e < nkc * PF_KC * WLD; e += 256) {
         const int ch = e / WLD, o = e - ch * WLD;
         wl[e] = (ch < a.Cin && o < a.Cout) ? a.w[(size_t)o * a.w_rs + (size_t)ch * a.w_cs] : 0.f;
@@ -191,6 +208,28 @@ __global__ __launch_bounds__(256, 2) void pointwise_fwd_kernel(PfArgs<T> a) {
             const long long t = wave_id + (s / nkc) * nwaves;
             const int b = (int)(t / tiles_per_b);
             const int p = (int)(t - (long long)b * tiles_per_b) * PF_COLS + 4 * l;
+            if constexpr (MAXPOOL) {   // relu?(fmaf(acc, scale, shift)), max over the group, one store per group and row
+                const int gl = a.mp.ns >> 2;                                  // lanes per group: 1, 2, 4, .., 32
+                const int m = (int)((unsigned)p / (unsigned)a.mp.ns), M = a.P / a.mp.ns;
+                const bool lead = (l & (gl - 1)) == 0 && p < a.P, orelu = a.mp.relu != 0;
+#pragma unroll
+                for (int ob = 0; ob < OB; ++ob)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int o = ob * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const float2 ss = *reinterpret_cast<const float2 *>(gm1 + 2 * o);
+                        float v0 = fmaf(acc[ob][0][r], ss.x, ss.y), v1 = fmaf(acc[ob][1][r], ss.x, ss.y);
+                        float v2 = fmaf(acc[ob][2][r], ss.x, ss.y), v3 = fmaf(acc[ob][3][r], ss.x, ss.y);
+                        if (orelu) { v0 = relu_nan(v0); v1 = relu_nan(v1); v2 = relu_nan(v2); v3 = relu_nan(v3); }
+                        float best = max_nan(max_nan(max_nan(v0, v1), v2), v3);
+#pragma unroll
+                        for (int d = 1; d < 32; d <<= 1)
+                            if (d < gl) best = max_nan(best, __shfl_xor(best, d, 32));
+                        if (lead && o < a.Cout) Payload<T>::st(a.y + ((size_t)b * a.Cout + o) * M + m, best);
+                        acc[ob][0][r] = 0.f; acc[ob][1][r] = 0.f; acc[ob][2][r] = 0.f; acc[ob][3][r] = 0.f;
+                    }
+                return;
+            }
             if (STATS) {   // the 128 columns of a channel live in the 32 lanes of one half-wave x 4 sub-tiles: exact two-pass
 #pragma unroll
                 for (int ob = 0; ob < OB; ++ob)
@@ -235,20 +274,21 @@ __global__ __launch_bounds__(256, 2) void pointwise_fwd_kernel(PfArgs<T> a) {
     }
 }
 
-template <int OB, typename T, bool STATS = false, bool GRAD = false>
+template <int OB, typename T, bool STATS = false, bool GRAD = false, bool MAXPOOL = false>
 static void launch_pf(const PfArgs<T> &a, hipStream_t st) {
     constexpr int WLD = OB == 1 ? 32 : 96, PF_KC = PfSlab<OB, GRAD>::KC;
     const int nkc = (a.Cin + PF_KC - 1) / PF_KC;
-    const int lds = nkc * PF_KC * (WLD + 4 + (GRAD ? 1 : 0)) * (int)sizeof(float);
+    const int lds = (nkc * PF_KC * (WLD + 4 + (GRAD ? 1 : 0)) + (MAXPOOL ? OB * 64 : 0)) * (int)sizeof(float);
     static int attr_lds = 0;
     if (lds > 65536 && lds > attr_lds) {
-        (void)hipFuncSetAttribute((const void *)pointwise_fwd_kernel<OB, T, STATS, GRAD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute((const void *)pointwise_fwd_kernel<OB, T, STATS, GRAD, MAXPOOL>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_lds = lds;
     }
     const long long ntiles = (long long)a.B * ((a.P + PF_COLS - 1) / PF_COLS);
     long long wgs = (ntiles + 3) / 4;
     if (wgs > 2048) wgs = 2048;   // 8 workgroups per CU; waves stride over the tiles
-    hipLaunchKernelGGL((pointwise_fwd_kernel<OB, T, STATS, GRAD>), dim3((unsigned)wgs), dim3(256), lds, st, a);
+    hipLaunchKernelGGL((pointwise_fwd_kernel<OB, T, STATS, GRAD, MAXPOOL>), dim3((unsigned)wgs), dim3(256), lds, st, a);
 }
 
 }  // namespace mgar
@@ -332,4 +372,51 @@ MGAR_API int mgar_pointwise_conv_fwd_maxgrad(const float *x4, int B, int Cin, in
     if (Cout <= 32) launch_pf<1, float, false, true>(a, st);
     else launch_pf<2, float, false, true>(a, st);
     return check_launch("pointwise_conv_fwd_maxgrad: launch failed");
+}
+
+// Inference tail of a shared MLP: [BN -> ReLU ->] conv 1x1 -> running-statistics BatchNorm [-> ReLU] -> max over nsample in one
+// launch (MAXPOOL epilogue above); the conv's output (B, Cout, M, nsample) is never written:
+//   pooled[b, o, m] = max_s relu?(fmaf(sum_i w[o, i] act_i(x[b, i, m, s]), out_scale[o], out_shift[o]))
+// NaN-propagating max and ReLU (csrc/common.hpp); a bf16 pooled value is rounded once, after the max.
+template <typename T>
+static int pointwise_conv_maxpool_eval_impl(const T *x, int B, int Cin, int M, int nsample, const float *w, int w_row_stride,
+                                            int w_col_stride, int Cout, const float *in_mean, const float *in_invstd,
+                                            const float *in_gamma, const float *in_beta, int in_relu, const float *out_scale,
+                                            const float *out_shift, int out_relu, T *pooled, void *stream) {
+    MGAR_REQUIRE(B >= 0 && Cin >= 0 && Cout >= 0 && M >= 0 && nsample >= 1, "pointwise_conv_maxpool_eval: bad sizes");
+    MGAR_REQUIRE((long long)M * nsample <= 2147483647LL - PF_COLS, "pointwise_conv_maxpool_eval: M * nsample too large");
+    if ((long long)B * M == 0 || Cout == 0) return MGAR_OK;
+    MGAR_REQUIRE(x && w && pooled && out_scale && out_shift, "pointwise_conv_maxpool_eval: null pointer");
+    MGAR_REQUIRE(in_mean == nullptr || in_invstd != nullptr, "pointwise_conv_maxpool_eval: in_mean without in_invstd");
+    if (Cout > 64 || Cin > 256 || Cin == 0 || (nsample & 3) != 0 || nsample > PF_COLS || PF_COLS % nsample != 0) {
+        set_error("pointwise_conv_maxpool_eval: needs 1 <= Cin <= 256, Cout <= 64 and nsample in {4, 8, 16, 32, 64, 128} (run "
+                  "mgar_pointwise_conv_fwd and mgar_bn_act_maxpool_fwd otherwise)");
+        return MGAR_EUNSUPPORTED;
+    }
+    const int P = M * nsample;
+    PfArgs<T> a{x, w, in_mean, in_invstd, in_gamma, in_beta, pooled, B, Cin, Cout, P, w_row_stride, w_col_stride, in_relu, nullptr,
+                {}, {out_scale, out_shift, nsample, out_relu}};
+    hipStream_t st = (hipStream_t)stream;
+    KtScope kt(KT_POINTWISE_FWD, st, (double)sizeof(T) * B * ((double)P * Cin + (double)M * Cout), 2.0 * (double)B * P * Cin * Cout);
+    if (Cout <= 32) launch_pf<1, T, false, false, true>(a, st);
+    else launch_pf<2, T, false, false, true>(a, st);
+    return check_launch("pointwise_conv_maxpool_eval: launch failed");
+}
+
+MGAR_API int mgar_pointwise_conv_maxpool_eval_fwd(const float *x, int B, int Cin, int M, int nsample, const float *w, int w_row_stride,
+                                                  int w_col_stride, int Cout, const float *in_mean, const float *in_invstd,
+                                                  const float *in_gamma, const float *in_beta, int in_relu, const float *out_scale,
+                                                  const float *out_shift, int out_relu, float *pooled, void *stream) {
+    return pointwise_conv_maxpool_eval_impl<float>(x, B, Cin, M, nsample, w, w_row_stride, w_col_stride, Cout, in_mean, in_invstd,
+                                                   in_gamma, in_beta, in_relu, out_scale, out_shift, out_relu, pooled, stream);
+}
+// bf16 payload: x and pooled address bf16 elements (called by name: no `_bf16` payload twin, see include/mgar_ops.h)
+MGAR_API int mgar_pointwise_conv_maxpool_eval_bf16_fwd(const void *x, int B, int Cin, int M, int nsample, const float *w,
+                                                       int w_row_stride, int w_col_stride, int Cout, const float *in_mean,
+                                                       const float *in_invstd, const float *in_gamma, const float *in_beta,
+                                                       int in_relu, const float *out_scale, const float *out_shift, int out_relu,
+                                                       void *pooled, void *stream) {
+    return pointwise_conv_maxpool_eval_impl<bf16_t>((const bf16_t *)x, B, Cin, M, nsample, w, w_row_stride, w_col_stride, Cout, in_mean,
+                                                    in_invstd, in_gamma, in_beta, in_relu, out_scale, out_shift, out_relu,
+                                                    (bf16_t *)pooled, stream);
 }

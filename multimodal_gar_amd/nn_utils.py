@@ -78,7 +78,8 @@ class PointwiseSequential(nn.Sequential):
     """nn.Sequential (same state-dict keys) for the shared MLPs: kernel-size-1 convolutions run as
     GEMMs, and on the device every BatchNorm [+ ReLU] that follows runs in the fused HIP kernels of
     csrc/bn_act.hip; ``forward_maxpool`` additionally folds the max over the last axis (nsample)
-    into the last BatchNorm + ReLU so that activation is never written."""
+    into the last BatchNorm + ReLU so that activation is never written.  In eval mode without a gradient the hidden
+    [BN -> ReLU -> conv] steps and the tail [conv -> BN -> ReLU -> max] stay on csrc/pointwise_fwd.hip (bn_ops.eval_mlp_plan)."""
 
     fuse_bn_conv = True
 
@@ -88,6 +89,9 @@ class PointwiseSequential(nn.Sequential):
         i, n = start, len(layers)
         pooled = False
         stats = input_stats          # BatchNorm statistics partials of the current x, if its producer kernel left them
+        # inference route (bn_ops.eval_mlp_plan): a pooled MLP whose group width the MAXPOOL epilogue does not take keeps the
+        # previous route as a whole, hidden steps included
+        eval_steps = not (pool_last and x.dim() == 4 and x.shape[3] not in bn_ops.EVAL_POOL_NSAMPLES)
         while i < n:
             layer = layers[i]
             # only the layer that consumes the input can hand its gradient back row-major
@@ -96,6 +100,14 @@ class PointwiseSequential(nn.Sequential):
                 # a conv with no BatchNorm in front (the module's first layer): the streaming kernel also leaves the statistics
                 # partials of its output for the BatchNorm that follows
                 feeds_bn = i + 1 < n and isinstance(layers[i + 1], _BN_TYPES) and layers[i + 1].training
+                if pool_last and x.is_cuda and self.fuse_bn_conv and x.dim() == 4 and i + 1 < n \
+                        and isinstance(layers[i + 1], _BN_TYPES) and not layers[i + 1].training:
+                    # inference, [conv -> BN -> ReLU -> max over ns] is all that is left: one launch, conv output never written
+                    relu2 = i + 2 < n and isinstance(layers[i + 2], nn.ReLU)
+                    if i + (3 if relu2 else 2) >= n:
+                        y = bn_ops.bn_act_conv_maxpool_eval(x, None, False, layer, layers[i + 1], relu2, others=layers[i + 2:n])
+                        if y is not None:
+                            return y, True
                 y = bn_ops.plain_conv(x, layer, want_out_stats=feeds_bn) if x.is_cuda and self.fuse_bn_conv else None
                 if y is not None:
                     x, stats = y if feeds_bn else (y, None)
@@ -115,13 +127,18 @@ class PointwiseSequential(nn.Sequential):
                     if nxt + (3 if relu2 else 2) >= n:
                         y = bn_ops.bn_act_conv_maxpool(x, layer, relu, layers[nxt], layers[nxt + 1], relu2, rowmajor_grad=rm,
                                                        in_stats=stats)
+                        if y is None and not layer.training:
+                            # inference: the same tail as one launch that never writes the conv's output (bn_ops.eval_mlp_plan)
+                            y = bn_ops.bn_act_conv_maxpool_eval(x, layer, relu, layers[nxt], layers[nxt + 1], relu2,
+                                                                others=layers[i + 1:nxt] + layers[nxt + 2:n])
                         if y is not None:
                             return y, True
                 if nxt < n and _is_pointwise(layers[nxt]) and self.fuse_bn_conv:
                     # [BN -> ReLU -> next conv] in one pass; the activated tensor is never written.  If a BatchNorm follows that
                     # conv, the kernel also leaves the statistics partials of its output (no statistics pass over it)
                     feeds_bn = nxt + 1 < n and isinstance(layers[nxt + 1], _BN_TYPES) and layers[nxt + 1].training
-                    y = bn_ops.bn_act_conv(x, layer, relu, layers[nxt], rowmajor_grad=rm, in_stats=stats, want_out_stats=feeds_bn)
+                    y = bn_ops.bn_act_conv(x, layer, relu, layers[nxt], rowmajor_grad=rm, in_stats=stats, want_out_stats=feeds_bn,
+                                           others=layers[i + 1:nxt], eval_steps=eval_steps)
                     if y is not None:
                         x, stats = y if feeds_bn else (y, None)
                         i = nxt + 1
