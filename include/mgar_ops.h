@@ -31,7 +31,7 @@ extern "C" {
 #define MGAR_EUNSUPPORTED (-3)/* size outside what the kernel was built for (e.g. nsample)   */
 
 #define MGAR_MAX_NSAMPLE 128   /* ball/voxel query: rows are staged in LDS                   */
-#define MGAR_ABI_VERSION 21  /* bumped on any signature change; mgar_abi_version() returns it */
+#define MGAR_ABI_VERSION 22 /* bumped on any signature change; mgar_abi_version() returns it */
 
 /* Library identity: the MGAR_ABI_VERSION it was compiled with and a static
  * description string of the last error on the calling thread. */
@@ -518,6 +518,25 @@ int mgar_pointwise_conv_maxpool_eval_fwd(const float *x, int B, int Cin, int M, 
                                          const float *in_invstd, const float *in_gamma, const float *in_beta, int in_relu,
                                          const float *out_scale, const float *out_shift, int out_relu, float *pooled,
                                          void *stream);
+
+/* mgar_pointwise_conv_fwd for bf16 payloads on the bf16 MFMA (csrc/pointwise_bf16.hip; ABI 22; forward only).  x (B, Cin, P)
+ * and y (B, Cout, P) address bf16 elements, 8-byte aligned; w and the BatchNorm vectors are fp32:
+ *   a[b,i,p] = bf16(act_i(float(x[b,i,p])))    act_i(v) = relu?(((v - in_mean[i]) * sc_i) + in_beta[i]), sc_i = in_invstd[i] *
+ *                                              in_gamma[i], every operation rounded to fp32 on its own (the prologue of
+ *                                              mgar_pointwise_conv_fwd); in_mean NULL = identity: a = x, nothing is rounded;
+ *                                              in_gamma / in_beta NULL = 1 / 0
+ *   w~[o,i]  = bf16(w[o*w_row_stride + i*w_col_stride])                 round to nearest even
+ *   y[b,o,p] = bf16(sum_i w~[o,i] * a[b,i,p])                           fp32 accumulation of exact products, rounded ONCE on store
+ * -- the contract of mgar_conv3d_bf16_fwd, the bf16 stem and mgar_spconv_bf16_fwd -- where mgar_pointwise_conv_fwd_bf16 (which
+ * keeps its meaning) multiplies the widened values with the fp32 weight.  A NaN stays a NaN through the roundings and the ReLU: a
+ * NaN in x makes its column of y NaN and no other.  No atomics, no cross-column state: a column's bits depend on that column of
+ * x, on w and on the BatchNorm vectors, not on B, P or the launch.  W is rounded by every workgroup: no pack kernel, no workspace.
+ * Needs 1 <= Cin <= 256, 1 <= Cout <= 64, P % 4 == 0 (MGAR_EUNSUPPORTED otherwise, nothing written); B * P == 0 is MGAR_OK and
+ * writes nothing.  Called by name: the `_bf16` is not at the end, so it is no payload twin of an fp32 entry point.
+ * Timer row pointwise_bf16_kernel: 2 (Cin + Cout) bytes and 2 Cin Cout flop per column. */
+int mgar_pointwise_mfma_bf16_fwd(const void *x, int B, int Cin, int P, const float *w, int w_row_stride, int w_col_stride,
+                                 int Cout, const float *in_mean, const float *in_invstd, const float *in_gamma,
+                                 const float *in_beta, int in_relu, void *y, void *stream);
 
 /* MaxPool3dSamePadding.forward of the reference's I3D (model/backbone.py:99-131): zero "same"
  * padding + max pooling without materialising the padded tensor.  x (NC, T, H, W) -> y (NC, ceil(T/st),

@@ -345,9 +345,11 @@ PLAIN_CONV_MAX_OUT = 32      # one 32-row output block (csrc/pointwise_fwd.hip O
 PLAIN_CONV_MAX_IN = 32
 
 
-def plain_conv(x, conv, want_out_stats=False):
+def plain_conv(x, conv, want_out_stats=False, bf16_mfma=False):
     """conv(x) for a bias-free kernel-size-1 ``conv`` that has no BatchNorm in front (the first layer of a shared MLP), or None
-    outside the kernel's shapes (the caller takes the library GEMM).  -> y, or (y, statistics partials | None)."""
+    outside the kernel's shapes (the caller takes the library GEMM).  -> y, or (y, statistics partials | None).  ``bf16_mfma``:
+    the caller's consent to the bf16-MFMA kernel for bf16 payloads (mlp_bf16_mfma_plan); PointwiseSequential withholds it where
+    an eval-mode BatchNorm follows (the inference route keeps its kernels)."""
     if not (x.is_cuda and x.dtype in _PAYLOADS and x.dim() >= 3 and conv.bias is None):
         return None
     if x.dtype != torch.float32 and torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
@@ -356,6 +358,11 @@ def plain_conv(x, conv, want_out_stats=False):
     x3 = x.contiguous().flatten(2)
     if c > PLAIN_CONV_MAX_IN or cout > PLAIN_CONV_MAX_OUT or x3.shape[2] % 4 != 0 or x3.shape[0] * x3.shape[2] < (1 << 16):
         return None
+    needs_grad = torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad)
+    if bf16_mfma and mlp_bf16_mfma_plan(x3, cout, needs_grad, None, PLAIN_CONV_MAX_IN, PLAIN_CONV_MAX_OUT):
+        y = _conv_bf16_mfma(x3, _f32(conv.weight.detach()).view(cout, c), None, None, None, None, False)
+        y = y.view(x.shape[0], cout, *x.shape[2:])
+        return (y, None) if want_out_stats else y   # bf16 has no statistics epilogue (stats_partial_buffer)
     out_stats = stats_partial_buffer(x3, cout, x3.shape[0] * x3.shape[2]) if want_out_stats and x3.shape[2] % STATS_TILE == 0 else None
     y = _PlainConv.apply(x3, _f32(conv.weight).view(cout, c), out_stats).view(x.shape[0], cout, *x.shape[2:])
     return (y, out_stats) if want_out_stats else y
@@ -370,6 +377,42 @@ FUSED_CONV_MAX_CHANNELS = 64   # csrc/pointwise_fwd.hip: Cout <= 64 in both dire
 
 
 FUSED_STATS_MAX_CHANNELS = 32   # csrc/pointwise_fwd.hip: the statistics epilogue exists for Cout <= 32
+
+
+# bf16 payloads that need no gradient take the bf16-MFMA forward kernel (csrc/pointwise_bf16.hip, mgar_pointwise_mfma_bf16_fwd)
+# in the train-mode / no-prologue steps of the shared MLPs -- bn_act_conv and plain_conv, inside their own shape gates -- where
+# mgar_pointwise_conv_fwd_bf16 widens every element and multiplies on the fp32 MFMA.  The activated input and the weight are
+# rounded to bf16 there (two roundings the widening route does not have).  MGAR_MLP_BF16_MFMA=0 (or this
+# flag) restores the widening route (A/B in tests and profiles).  The inference route (eval_mlp_plan) is not touched.
+MLP_BF16_MFMA = os.environ.get("MGAR_MLP_BF16_MFMA", "1") != "0"
+
+
+def mlp_bf16_mfma_plan(x, cout, needs_grad, bn=None, max_in=FUSED_CONV_MAX_CHANNELS, max_out=FUSED_CONV_MAX_CHANNELS):
+    """True where conv(relu?(bn(x))) -- ``bn`` None: conv(x) -- goes to mgar_pointwise_mfma_bf16_fwd.  Decided from attributes
+    alone (x.dtype, x.is_cuda, x.shape, bn.training, the caller's ``needs_grad``, the switch): no tensor is read, nothing
+    synchronises.  All of: the switch is on; x is a bf16 device tensor (B, C, ...); no gradient is needed; the BatchNorm, if
+    any, is in training mode (the inference route keeps its kernels); 1 <= C <= max_in, 1 <= Cout <= max_out (the caller's
+    gates: 64 / 64 for bn_act_conv, 32 / 32 for plain_conv); P % 4 == 0; B * P >= 65 536."""
+    if not (MLP_BF16_MFMA and x.dtype == torch.bfloat16 and x.is_cuda and len(x.shape) >= 3) or needs_grad:
+        return False
+    if bn is not None and not bn.training:
+        return False
+    c, p = x.shape[1], 1
+    for s in x.shape[2:]:
+        p *= s
+    return 1 <= c <= max_in and 1 <= cout <= max_out and p % 4 == 0 and x.shape[0] * p >= EVAL_MIN_COLUMNS
+
+
+def _conv_bf16_mfma(x3, w, mean, invstd, gamma, beta, relu):
+    """x3 (B, C, P) bf16, w (Cout, C) fp32 -> (B, Cout, P) bf16 on csrc/pointwise_bf16.hip; mean None: no prologue.  No autograd
+    node: the callers take it only where no gradient is needed."""
+    b, c, p = x3.shape
+    cout = w.shape[0]
+    w = w.contiguous()
+    y = torch.empty((b, cout, p), dtype=torch.bfloat16, device=x3.device)
+    L.call("mgar_pointwise_mfma_bf16_fwd", L.pptr(x3, torch.bfloat16), b, c, p, L.fptr(w), c, 1, cout, L.fptr(mean), L.fptr(invstd),
+           L.fptr(gamma), L.fptr(beta), int(relu), L.pptr(y, torch.bfloat16), L.stream_of(x3))
+    return y
 
 
 # Inference (every BatchNorm on running statistics, no gradient) keeps the shared MLPs on csrc/pointwise_fwd.hip: a hidden
@@ -484,6 +527,11 @@ def bn_act_conv(x, bn, relu, conv, rowmajor_grad=False, in_stats=None, want_out_
         return None
     mean, invstd = _stats(x3, bn, in_stats)
     gamma, beta = _affine(bn, c, x.device)
+    needs_grad = torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or gamma.requires_grad or beta.requires_grad)
+    if mlp_bf16_mfma_plan(x3, cout, needs_grad, bn):
+        y = _conv_bf16_mfma(x3, _f32(conv.weight.detach()).view(cout, c), mean, invstd, gamma.detach(), beta.detach(), relu)
+        y = y.view(x.shape[0], cout, *x.shape[2:])
+        return (y, None) if want_out_stats else y   # bf16 has no statistics epilogue (stats_partial_buffer)
     out_stats = stats_partial_buffer(x3, cout, x3.shape[0] * x3.shape[2]) \
         if want_out_stats and cout <= FUSED_STATS_MAX_CHANNELS and x3.shape[2] % STATS_TILE == 0 else None
     y = _BnActConv.apply(x3, gamma, beta, mean, invstd, relu, _f32(conv.weight).view(cout, c), rowmajor_grad, out_stats)

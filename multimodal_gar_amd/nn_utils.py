@@ -108,7 +108,10 @@ class PointwiseSequential(nn.Sequential):
                         y = bn_ops.bn_act_conv_maxpool_eval(x, None, False, layer, layers[i + 1], relu2, others=layers[i + 2:n])
                         if y is not None:
                             return y, True
-                y = bn_ops.plain_conv(x, layer, want_out_stats=feeds_bn) if x.is_cuda and self.fuse_bn_conv else None
+                # bf16 payloads: the bf16-MFMA kernel, unless an eval-mode BatchNorm follows (the inference route is not moved)
+                eval_bn = i + 1 < n and isinstance(layers[i + 1], _BN_TYPES) and not layers[i + 1].training
+                y = bn_ops.plain_conv(x, layer, want_out_stats=feeds_bn, bf16_mfma=not eval_bn) \
+                    if x.is_cuda and self.fuse_bn_conv else None
                 if y is not None:
                     x, stats = y if feeds_bn else (y, None)
                 else:
