@@ -613,6 +613,29 @@ int mgar_conv3d_k3_bf16_fwd_affine(const void *x, int N, int Cin, int D, int H, 
                                    const float *scale, const float *shift, int relu, void *y, long long y_batch_stride,
                                    void *stream);
 
+/* The 1x1x1 units of Inception-I3D (model/backbone.py:134-206 with kernel_shape [1, 1, 1]: ``Conv3d_2b_1x1`` and four units per
+ * InceptionModule) for bf16 payloads on the bf16 MFMA (csrc/conv1x1_bf16.hip; ABI 22; forward only): per sample the product
+ * Y[n] (Cout, P) = W (Cout, Cin) . X[n] (Cin, P), P = T * H * W, on the NCDHW tensor as it lies.  x (N, Cin, P) bf16 contiguous;
+ * w (Cout, Cin) fp32 row-major (the master weight, or a bf16 weight widened exactly); element (n, o, p) of y (bf16) lies at
+ * y + n * y_batch_stride + o * P + p, so y may be the channel slice Y[:, c0 : c0 + Cout] of a wider contiguous NCDHW tensor.
+ *   w~[o,i]    = bf16(w[o * Cin + i])                                     round to nearest even
+ *   acc[n,o,p] = sum_i w~[o,i] * x[n,i,p]                                 fp32, exact products, 16-channel k-steps ascending
+ *   mgar_conv1x1_bf16_fwd:        y = bf16(acc)
+ *   mgar_conv1x1_bf16_fwd_affine: v = fmaf(acc, scale[o], shift[o]);  y = bf16(relu ? (v <= 0 ? +0 : v) : v)     (NaN: v)
+ * -- the contract of mgar_pointwise_mfma_bf16_fwd and mgar_conv3d_k3_bf16_fwd[_affine]: one rounding of the payload, a NaN stays a
+ * NaN through the ReLU and the rounding and reaches its own column only.  scale, shift (Cout) fp32, both required.  No atomics,
+ * no cross-column state: a column's bits depend on that column of x, on w and on scale / shift, not on N, P, y_batch_stride or
+ * the launch.  W is rounded into LDS by every workgroup, in chunks where it does not fit: no pack kernel, no workspace.
+ * Needs 1 <= Cin <= 1024, 1 <= Cout <= 512, P % 4 == 0, x and y 8-byte aligned, y_batch_stride % 4 == 0: MGAR_EUNSUPPORTED
+ * otherwise, nothing launched (callers fall back to the library GEMM / convolution); y_batch_stride < Cout * P or a null pointer
+ * is MGAR_EINVAL; N * P == 0 is MGAR_OK and writes nothing.  Called by name (the `_bf16` is not at the end: no payload twin).
+ * Timer row conv1x1_bf16_kernel: 2 (Cin + Cout) bytes and 2 Cin Cout flop per column. */
+int mgar_conv1x1_bf16_fwd(const void *x, int N, int Cin, int P, const float *w, int Cout,
+                          void *y, long long y_batch_stride, void *stream);
+int mgar_conv1x1_bf16_fwd_affine(const void *x, int N, int Cin, int P, const float *w, int Cout,
+                                 const float *scale, const float *shift, int relu,
+                                 void *y, long long y_batch_stride, void *stream);
+
 /* ===================== third-party ops on the hot path ================================ */
 
 /* torchvision.ops.roi_align (call site model/gat_model.py:1056-1057, sg_model.py:96-97).

@@ -138,7 +138,7 @@ class Unit3D(nn.Module):
                        L.stream_of(x))
         return y
 
-    gemm_1x1 = os.environ.get("MGAR_I3D_GEMM_1X1", "1") != "0"        # 1x1x1 units on the device: library GEMMs (one per sample) instead of the library convolution
+    gemm_1x1 = os.environ.get("MGAR_I3D_GEMM_1X1", "1") != "0"        # 1x1x1 units on the device: library GEMMs (one per sample) instead of the library convolution; bf16 payloads: k1_bf16 below
     wino_kernel = os.environ.get("MGAR_I3D_OWN_CONV", "1") != "0"     # 3x3x3, stride 1 on the device: csrc/conv3d_wino.hip (Winograd F(2,3) along W on the fp32 MFMA); bf16 payloads: csrc/conv3d_bf16.hip (direct, bf16 MFMA)
 
     def _k3_bf16_route(self, x):
@@ -191,6 +191,48 @@ class Unit3D(nn.Module):
         L.call("mgar_conv3d_k3_fwd", L.fptr(x), n, cin, d, h, w, L.fptr(wf), c.out_channels, L.fptr(wp), L.fptr(y), L.stream_of(x))
         return y
 
+    k1_bf16 = os.environ.get("MGAR_I3D_K1_BF16", "0") != "0"          # 1x1x1 units on bf16 payloads: csrc/conv1x1_bf16.hip (bf16 MFMA, one launch for all samples) instead of the per-sample library GEMMs; inside gemm_1x1.  Off by default: c2's step did not clear the bar
+
+    K1_MAX_IN, K1_MAX_OUT = 1024, 512                                   # mgar_conv1x1_bf16_fwd's channel range
+
+    def _k1_bf16_route(self, x):
+        """_k1_conv_bf16 takes x (attributes only)"""
+        c = self.conv3d
+        return bool(self.gemm_1x1 and self.k1_bf16 and x.is_cuda and x.dim() == 5 and x.dtype == torch.bfloat16 and x.is_contiguous()
+                    and self._kernel_shape == (1, 1, 1) and self._stride == (1, 1, 1) and c.groups == 1 and c.bias is None
+                    and c.weight.dtype in (torch.bfloat16, torch.float32)
+                    and (x.shape[2] * x.shape[3] * x.shape[4]) % 4 == 0
+                    and 1 <= c.in_channels <= self.K1_MAX_IN and 1 <= c.out_channels <= self.K1_MAX_OUT
+                    and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad)))
+
+    def _k1_weight(self):
+        """The (Cout, Cin) fp32 weight mgar_conv1x1_bf16_fwd reads (a bf16 weight widened exactly; the kernel rounds to bf16), cached
+        on the unit and keyed on the weight's data_ptr and _version as sparse_ops.fold_bn keys its result: the frozen trunk launches
+        no conversion per call, an in-place update or a replaced .data recomputes."""
+        w = self.conv3d.weight
+        key = (w.data_ptr(), w._version, w.device, w.dtype)
+        cached = self.__dict__.get("_mgar_k1_weight")
+        if cached is None or cached[0] != key:
+            with torch.no_grad(), torch.autocast(device_type=w.device.type, enabled=False):
+                wf = w.detach().reshape(self.conv3d.out_channels, self.conv3d.in_channels).float().contiguous()
+            cached = (key, wf)
+            self.__dict__["_mgar_k1_weight"] = cached
+        return cached[1]
+
+    def _k1_conv_bf16(self, x):
+        """bf16 payloads (autocast on or off): the unit as ONE launch of csrc/conv1x1_bf16.hip for all samples, bf16 NCDHW in and
+        out, the weight as in _k3_conv_bf16.  Or None."""
+        if not self._k1_bf16_route(x):
+            return None
+        from .. import _lib as L
+        c = self.conv3d
+        n, cin, d, h, w = x.shape
+        p = d * h * w
+        y = torch.empty((n, c.out_channels, d, h, w), dtype=torch.bfloat16, device=x.device)
+        L.call("mgar_conv1x1_bf16_fwd", L.pptr(x, torch.bfloat16), n, cin, p, L.fptr(self._k1_weight()), c.out_channels,
+               L.pptr(y, torch.bfloat16), c.out_channels * p, L.stream_of(x))
+        return y
+
     def _conv(self, x):
         pads = _same_pads(x.shape[2:], self._kernel_shape, self._stride)
         stem = self._stem_conv(x)
@@ -199,6 +241,9 @@ class Unit3D(nn.Module):
         k3 = self._k3_conv(x)
         if k3 is not None:
             return k3
+        k1 = self._k1_conv_bf16(x)
+        if k1 is not None:
+            return k1
         if (self.gemm_1x1 and x.is_cuda and x.dim() == 5 and self._kernel_shape == (1, 1, 1) and self._stride == (1, 1, 1)
                 and x.is_contiguous() and self.conv3d.groups == 1
                 and (not torch.is_autocast_enabled() or x.dtype == torch.bfloat16)     # operands already bf16: nothing for autocast to cast (out= GEMMs are not re-cast)
@@ -266,20 +311,33 @@ class Unit3D(nn.Module):
     # restores convolution + bn_ops.bn_act (A/B in tests and profiles).
     fold_bn_eval = os.environ.get("MGAR_I3D_FOLD_BN", "1") != "0"
 
+    def _eval_foldable(self, x):
+        """the conditions eval_fold_plan and eval_fold_plan_1x1 share: the switch, an eval-mode BatchNorm with running statistics,
+        ReLU or no activation, no channels-last output, nothing that needs a gradient"""
+        if not (self.fold_bn_eval and self._use_batch_norm and (self._activation_fn is F.relu or self._activation_fn is None)
+                and not self.emit_channels_last):
+            return False
+        bn = self.bn
+        if bn.training or not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or self.conv3d.weight.requires_grad
+                                        or (bn.affine and (bn.weight.requires_grad or bn.bias.requires_grad))):
+            return False
+        return True
+
+    def eval_fold_plan_1x1(self, x):
+        """'k1_bf16' where a 1x1x1 unit runs on x as one launch of mgar_conv1x1_bf16_fwd_affine -- eval_fold_plan's conditions on
+        the BatchNorm, the activation, gradients and emit_channels_last, plus _k1_bf16_route(x) -- or None.  Pure.  forward
+        consults it where eval_fold_plan (which never folds a 1x1x1 unit) returns None."""
+        return 'k1_bf16' if self._eval_foldable(x) and self._k1_bf16_route(x) else None
+
     def eval_fold_plan(self, x):
         """Which *_affine entry point runs this unit on x in one launch: 'stem', 'k3' (fp32) or 'k3_bf16' -- or None for the
         convolution + BatchNorm path.  Pure: reads attributes of x and of the unit, touches no tensor.  Folded when the switch is
         on, the BatchNorm is in eval mode with running statistics, the activation is ReLU or none, nothing asks for a gradient
         (input, convolution weight, BatchNorm affine parameters), the unit does not emit channels-last, and the unit's own
         convolution kernel takes x (_stem_route / _k3_route / _k3_bf16_route); 1x1x1 units never are."""
-        if not (self.fold_bn_eval and self._use_batch_norm and (self._activation_fn is F.relu or self._activation_fn is None)
-                and not self.emit_channels_last):
-            return None
-        bn = self.bn
-        if bn.training or not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
-            return None
-        if torch.is_grad_enabled() and (x.requires_grad or self.conv3d.weight.requires_grad
-                                        or (bn.affine and (bn.weight.requires_grad or bn.bias.requires_grad))):
+        if not self._eval_foldable(x):
             return None
         if self._stem_route(x):
             return 'stem'
@@ -289,8 +347,9 @@ class Unit3D(nn.Module):
 
     def _conv_folded(self, x, route, out):
         """One call of the route's *_affine entry point: [relu](bn(conv(x))) with bn as sparse_ops.fold_bn's cached (scale, shift).
-        A 3x3x3 unit writes into ``out`` where that is a channel slice of a wider contiguous tensor (bn_ops._slice_stride) the
-        kernel's store can address (even batch stride; fp32: 8-byte aligned pairs); into a fresh tensor otherwise."""
+        A 3x3x3 or 1x1x1 unit writes into ``out`` where that is a channel slice of a wider contiguous tensor (bn_ops._slice_stride)
+        the kernel's store can address (even batch stride; fp32: 8-byte aligned pairs; 1x1x1: batch stride % 4 == 0 and an 8-byte
+        aligned base); into a fresh tensor otherwise."""
         from .. import _lib as L, bn_ops, sparse_ops
         c = self.conv3d
         scale, shift = sparse_ops.fold_bn(self.bn)
@@ -312,10 +371,15 @@ class Unit3D(nn.Module):
         bstride = bn_ops._slice_stride(out, _Like((n, cout, d, h, w), dt))
         if bstride is not None and (bstride % 2 != 0 or out.data_ptr() % (8 if dt == torch.float32 else 2) != 0):
             bstride = None
+        if route == 'k1_bf16' and bstride is not None and (bstride % 4 != 0 or out.data_ptr() % 8 != 0):
+            bstride = None                                  # 8-byte stores: the slice starts on one and every sample does
         y = out if bstride is not None else torch.empty((n, cout, d, h, w), dtype=dt, device=x.device)
         if bstride is None:
             bstride = cout * d * h * w
-        if route == 'k3':
+        if route == 'k1_bf16':
+            L.call("mgar_conv1x1_bf16_fwd_affine", L.pptr(x, torch.bfloat16), n, cin, d * h * w, L.fptr(self._k1_weight()), cout,
+                   L.fptr(scale), L.fptr(shift), relu, y.data_ptr(), bstride, L.stream_of(x))
+        elif route == 'k3':
             wp = torch.empty((L.raw("mgar_conv3d_k3_workspace_floats", cin, cout),), dtype=torch.float32, device=x.device)
             wf = c.weight.detach().contiguous()
             L.call("mgar_conv3d_k3_fwd_affine", L.fptr(x), n, cin, d, h, w, L.fptr(wf), cout, L.fptr(wp), L.fptr(scale), L.fptr(shift),
@@ -331,7 +395,7 @@ class Unit3D(nn.Module):
         """``out`` (optional): a channel slice y[:, c0:c1] of a wider tensor the result should land in (the caller's
         concatenation); honoured where the fused BatchNorm + ReLU kernel (or, in eval mode, the convolution's own store) writes
         the result, ignored otherwise -- the caller checks ``result is out``."""
-        route = self.eval_fold_plan(x)
+        route = self.eval_fold_plan(x) or self.eval_fold_plan_1x1(x)
         if route is not None:
             return self._conv_folded(x, route, out)
         return self._bn_relu(self._conv(x), out)
