@@ -538,6 +538,43 @@ int mgar_pointwise_mfma_bf16_fwd(const void *x, int B, int Cin, int P, const flo
                                  int Cout, const float *in_mean, const float *in_invstd, const float *in_gamma,
                                  const float *in_beta, int in_relu, void *y, void *stream);
 
+/* The WIDE layers of the shared MLPs -- more than 64 channels on either side -- for bf16 payloads on the bf16 MFMA
+ * (csrc/pointwise_wide_bf16.hip; forward only), with the previous BatchNorm [+ ReLU] as a prologue and, optionally, the next
+ * eval-mode BatchNorm [+ ReLU] [+ max over nsample] in the store.  x (B, Cin, P) bf16 contiguous; w fp32 with rows w_ld floats
+ * apart (w_ld >= Cin: w may be a column slice W[:, c0 : c0 + Cin] of a wider row-major matrix, at any 4-byte alignment); the
+ * vectors are fp32:
+ *   a[b,i,p] = bf16(act_i(float(x[b,i,p])))    act_i(v) = relu?(((v - in_mean[i]) * sc_i) + in_beta[i]), sc_i = in_invstd[i] *
+ *                                              in_gamma[i], every operation rounded to fp32 on its own (the prologue of
+ *                                              mgar_pointwise_mfma_bf16_fwd); in_mean NULL = identity: a = x; in_gamma / in_beta
+ *                                              NULL = 1 / 0
+ *   w~[o,i]  = bf16(w[o * w_ld + i])                                     round to nearest even
+ *   acc      = sum_i w~[o,i] * a[b,i,p]                                  fp32, exact products, 16-channel k-steps ascending
+ *   mgar_pointwise_wide_bf16_fwd, out_scale NULL:  y[b,o,p] = bf16(acc)
+ *   mgar_pointwise_wide_bf16_fwd, out_scale given: v = fmaf(acc, out_scale[o], out_shift[o]);
+ *                                                  y[b,o,p] = bf16(out_relu ? (v <= 0 ? +0 : v) : v)              (NaN: v)
+ *   mgar_pointwise_wide_maxpool_bf16_fwd:          x (B, Cin, M, ns), y (B, Cout, M) contiguous:
+ *                                                  y[b,o,m] = bf16(max over s < ns of that v at column m * ns + s)
+ * -- the contract of mgar_pointwise_mfma_bf16_fwd and mgar_conv1x1_bf16_fwd[_affine]: one rounding of the payload (pooled: after
+ * the max); a NaN stays a NaN through the roundings, both ReLUs and the max (as in mgar_pointwise_conv_maxpool_eval_fwd) and
+ * reaches its own column (pooled: its own group) only.  Element (b, o, p) of the unpooled y lies at y + b * y_batch_stride +
+ * o * P + p.  No atomics, no cross-column state: a column's (group's) bits depend on that column (group) of x, on w and on the
+ * vectors, not on B, P, y_batch_stride or the launch.  W is rounded into LDS by every workgroup, in chunks where it does not
+ * fit: no pack kernel, no workspace.
+ * Needs 1 <= Cin <= 1024, 1 <= Cout <= 512, P % 4 == 0, w_ld >= Cin, x and y 8-byte aligned, y_batch_stride % 4 == 0, ns in
+ * {4, 8, 16, 32, 64, 128}: MGAR_EUNSUPPORTED otherwise, nothing launched (callers fall back to the library GEMM);
+ * y_batch_stride < Cout * P, a null pointer, out_scale without out_shift (the pooled entry requires both) or in_mean without
+ * in_invstd is MGAR_EINVAL; B * P == 0 is MGAR_OK and writes nothing.  Called by name (the `_bf16` is not at the end: no payload
+ * twin).  Timer row pointwise_wide_bf16_kernel: 2 Cin bytes per column plus 2 Cout per column (pooled: per group) and
+ * 2 Cin Cout flop per column. */
+int mgar_pointwise_wide_bf16_fwd(const void *x, int B, int Cin, int P, const float *w, int w_ld, int Cout,
+                                 const float *in_mean, const float *in_invstd, const float *in_gamma, const float *in_beta,
+                                 int in_relu, const float *out_scale, const float *out_shift, int out_relu, void *y,
+                                 long long y_batch_stride, void *stream);
+int mgar_pointwise_wide_maxpool_bf16_fwd(const void *x, int B, int Cin, int M, int ns, const float *w, int w_ld, int Cout,
+                                         const float *in_mean, const float *in_invstd, const float *in_gamma,
+                                         const float *in_beta, int in_relu, const float *out_scale, const float *out_shift,
+                                         int out_relu, void *y, void *stream);
+
 /* MaxPool3dSamePadding.forward of the reference's I3D (model/backbone.py:99-131): zero "same"
  * padding + max pooling without materialising the padded tensor.  x (NC, T, H, W) -> y (NC, ceil(T/st),
  * ceil(H/sh), ceil(W/sw)).  Forward only (I3D is frozen in MGAR-net). */

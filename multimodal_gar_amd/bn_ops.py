@@ -509,6 +509,121 @@ def _bn_act_conv_eval(x, bn, relu, conv, others):
     return y.view(x.shape[0], cout, *x.shape[2:])
 
 
+# bf16 payloads that need no gradient take csrc/pointwise_wide_bf16.hip in the shared-MLP layers with MORE than 64 channels on
+# either side (SA levels 2-4, the FP modules, the FP projections): [BN -> ReLU ->] conv as one launch where the route above runs
+# the statistics pass, mgar_bn_act_fwd_bf16 and a batched library GEMM, and in eval mode the tail [BN -> ReLU ->] conv -> BN
+# [-> ReLU] [-> max over nsample] as one launch.  Every shape the narrow kernels or plain_conv take
+# stays where it is.  MGAR_MLP_BF16_WIDE (or this flag) switches it; MGAR_MLP_EVAL_FUSE=0 switches its eval-mode forms off too.
+MLP_BF16_WIDE = os.environ.get("MGAR_MLP_BF16_WIDE", "1") != "0"
+WIDE_MAX_IN, WIDE_MAX_OUT = 1024, 512          # mgar_pointwise_wide_bf16_fwd: 1 <= Cin <= 1024, 1 <= Cout <= 512
+# The plan is NARROWER than the kernel.  Per shape (profiles/README.md, tools/pointwise_wide_bf16.py) the kernel beats bn_act +
+# library GEMM [+ bn_act_maxpool] by 1.26 - 2.5x wherever both channel counts are at most 128 and loses from Cin = 196 up (0.34 -
+# 0.82x: G waves re-read the x tile through the L1, which is the limit there, not HBM); 128 -> 196 and 96 -> 256 are a draw.
+# So the host routes the kernel up to 128 / 128 and everything wider keeps the library GEMM.  Tests lift the two gates.
+WIDE_PLAN_MAX_IN, WIDE_PLAN_MAX_OUT = 128, 128
+WIDE_FWD, WIDE_POOL = "mgar_pointwise_wide_bf16_fwd", "mgar_pointwise_wide_maxpool_bf16_fwd"
+
+
+def mlp_bf16_wide_plan(x, conv, bn=None, bn2=None, others=(), pool=False, cin=None):
+    """True where bn2?(conv(relu?(bn(x)))) [-> max over the last axis: ``pool``] goes to csrc/pointwise_wide_bf16.hip.  ``bn``
+    None: the conv reads x itself; ``bn2`` None: the plain store; ``others``: further modules the step swallows (the ReLUs);
+    ``cin``: the conv applies a column slice of its weight to x's ``cin`` channels (the FP projections).  Decided from
+    attributes alone -- no tensor is read, nothing synchronises.  All of: the switch is on; x is a bf16 device tensor
+    (B, C, ...); no gradient is required (grad mode off, or neither x nor a parameter of these layers requires one); the conv
+    is point-wise and bias-free; max(C, Cout) > 64 (everything else stays on the narrow kernels); C <= 1024, Cout <= 512 (the
+    kernel's limits) and C <= WIDE_PLAN_MAX_IN, Cout <= WIDE_PLAN_MAX_OUT (128 / 128: where the kernel was measured to win);
+    P % 4 == 0; B * P >= 65 536; no forward (pre-)hook on these layers; every eval-mode BatchNorm has running statistics and
+    MLP_EVAL_FUSE is on; bn2 is in eval mode; ``pool``: x (B, C, M, ns) with ns in EVAL_POOL_NSAMPLES and a bn2; the library
+    has the symbol."""
+    from .nn_utils import _BN_TYPES, _is_pointwise
+    if not (MLP_BF16_WIDE and x.dtype == torch.bfloat16 and x.is_cuda and len(x.shape) >= 3):
+        return False
+    if (WIDE_POOL if pool else WIDE_FWD) not in L._fns:
+        return False
+    mods = [m for m in (bn, conv, bn2) + tuple(others) if m is not None]
+    for m in (bn, bn2):
+        if m is None:
+            continue
+        if not isinstance(m, _BN_TYPES):
+            return False
+        if not m.training and not (MLP_EVAL_FUSE and m.track_running_stats and m.running_mean is not None
+                                   and m.running_var is not None):
+            return False
+    if bn2 is not None and bn2.training:
+        return False
+    if not _is_pointwise(conv) or conv.bias is not None:
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in mods for p in m.parameters(recurse=False))):
+        return False
+    if any(m._forward_hooks or m._forward_pre_hooks for m in mods):
+        return False
+    c, cout = x.shape[1], conv.out_channels
+    if (conv.in_channels != c if cin is None else cin != c) or (bn is not None and bn.num_features != c) \
+            or (bn2 is not None and bn2.num_features != cout):
+        return False
+    if max(c, cout) <= FUSED_CONV_MAX_CHANNELS or not (1 <= c <= WIDE_MAX_IN and 1 <= cout <= WIDE_MAX_OUT):
+        return False
+    if c > WIDE_PLAN_MAX_IN or cout > WIDE_PLAN_MAX_OUT:
+        return False
+    p = 1
+    for s in x.shape[2:]:
+        p *= s
+    if p % 4 != 0 or x.shape[0] * p < EVAL_MIN_COLUMNS:
+        return False
+    if pool and not (bn2 is not None and len(x.shape) == 4 and x.shape[3] in EVAL_POOL_NSAMPLES):
+        return False
+    return True
+
+
+def _wide_launch(x3, w, w_ld, cout, pro, relu, epi, relu2, ns=0):
+    """x3 (B, C, P) bf16 contiguous; w: fp32 device tensor whose element (o, i) lies w_ld * o + i floats behind its data pointer;
+    pro = (mean, invstd, gamma, beta) | None; epi = (scale, shift) | None; ns: the pooled entry.  No autograd node."""
+    b, c, p = x3.shape
+    mean, invstd, gamma, beta = pro if pro is not None else (None,) * 4
+    scale, shift = epi if epi is not None else (None, None)
+    if w.dtype != torch.float32 or not w.is_cuda:
+        raise L.MgarError("the wide bf16 kernel takes an fp32 device weight")
+    xp, st = L.pptr(x3, torch.bfloat16), L.stream_of(x3)
+    if ns:
+        y = torch.empty((b, cout, p // ns), dtype=torch.bfloat16, device=x3.device)
+        L.call(WIDE_POOL, xp, b, c, p // ns, ns, w.data_ptr(), w_ld, cout, L.fptr(mean), L.fptr(invstd), L.fptr(gamma), L.fptr(beta),
+               int(relu), L.fptr(scale), L.fptr(shift), int(relu2), L.pptr(y, torch.bfloat16), st)
+    else:
+        y = torch.empty((b, cout, p), dtype=torch.bfloat16, device=x3.device)
+        L.call(WIDE_FWD, xp, b, c, p, w.data_ptr(), w_ld, cout, L.fptr(mean), L.fptr(invstd), L.fptr(gamma), L.fptr(beta),
+               int(relu), L.fptr(scale), L.fptr(shift), int(relu2), L.pptr(y, torch.bfloat16), cout * p, st)
+    return y
+
+
+def conv_bf16_wide(x, conv, bn=None, relu=False, bn2=None, relu2=False, pool=False, others=(), in_stats=None, cols=None):
+    """bn2?(conv(relu?(bn(x)))) [-> max over the last axis] as ONE launch of csrc/pointwise_wide_bf16.hip, or None where
+    mlp_bf16_wide_plan refuses (the caller keeps its route).  bn in training mode enters with its batch statistics (_stats, as
+    bn_act_conv), in eval mode with its running ones; bn2 enters as sparse_ops.fold_bn's (scale, shift).  ``cols`` = (c0, c1):
+    the conv's weight columns c0 .. c1 - 1 applied to x's c1 - c0 channels (no copy: the kernel reads the slice in place).  An x
+    that is not 8-byte aligned (only the address is looked at) is refused here too, so the entry point's MGAR_EUNSUPPORTED is
+    never reached from the host."""
+    cin = None if cols is None else cols[1] - cols[0]
+    if not mlp_bf16_wide_plan(x, conv, bn, bn2, others, pool, cin):
+        return None
+    c, cout = x.shape[1], conv.out_channels
+    x3 = x.contiguous().flatten(2)
+    if x3.data_ptr() % 8 != 0:      # a view whose storage offset breaks the kernel's 8-byte alignment: the caller's route
+        return None
+    wfull = _f32(conv.weight.detach()).reshape(cout, conv.in_channels)
+    wfull = wfull if wfull.is_contiguous() else wfull.contiguous()
+    w = wfull if cols is None else wfull[:, cols[0]:cols[1]]
+    pro = epi = None
+    if bn is not None:
+        mean, invstd = _stats(x3, bn, in_stats)
+        gamma, beta = _affine(bn, c, x.device)
+        pro = (mean, invstd, gamma.detach(), beta.detach())
+    if bn2 is not None:
+        from .sparse_ops import fold_bn
+        epi = fold_bn(bn2)
+    y = _wide_launch(x3, w, conv.in_channels, cout, pro, relu, epi, relu2, x.shape[3] if pool else 0)
+    return y if pool else y.view(x.shape[0], cout, *x.shape[2:])
+
+
 def bn_act_conv(x, bn, relu, conv, rowmajor_grad=False, in_stats=None, want_out_stats=False, others=(), eval_steps=True):
     """conv(relu?(bn(x))) for a bias-free kernel-size-1 ``conv`` in one fused step, or None if the
     shapes are outside the fused kernel (the caller then runs bn_act and the GEMM separately).  ``others``, ``eval_steps``: the

@@ -79,7 +79,9 @@ class PointwiseSequential(nn.Sequential):
     GEMMs, and on the device every BatchNorm [+ ReLU] that follows runs in the fused HIP kernels of
     csrc/bn_act.hip; ``forward_maxpool`` additionally folds the max over the last axis (nsample)
     into the last BatchNorm + ReLU so that activation is never written.  In eval mode without a gradient the hidden
-    [BN -> ReLU -> conv] steps and the tail [conv -> BN -> ReLU -> max] stay on csrc/pointwise_fwd.hip (bn_ops.eval_mlp_plan)."""
+    [BN -> ReLU -> conv] steps and the tail [conv -> BN -> ReLU -> max] stay on csrc/pointwise_fwd.hip (bn_ops.eval_mlp_plan).
+    bf16 payloads without a gradient take csrc/pointwise_wide_bf16.hip in the layers with more than 64 channels on either side
+    (bn_ops.mlp_bf16_wide_plan)."""
 
     fuse_bn_conv = True
 
@@ -106,8 +108,15 @@ class PointwiseSequential(nn.Sequential):
                     relu2 = i + 2 < n and isinstance(layers[i + 2], nn.ReLU)
                     if i + (3 if relu2 else 2) >= n:
                         y = bn_ops.bn_act_conv_maxpool_eval(x, None, False, layer, layers[i + 1], relu2, others=layers[i + 2:n])
+                        if y is None:    # the same tail on the wide bf16 kernel (bn_ops.mlp_bf16_wide_plan)
+                            y = bn_ops.conv_bf16_wide(x, layer, bn2=layers[i + 1], relu2=relu2, pool=True, others=layers[i + 2:n])
                         if y is not None:
                             return y, True
+                y = self._wide_conv_step(x, layers, None, i, False, pool_last, eval_steps, None) if x.is_cuda and self.fuse_bn_conv \
+                    else None
+                if y is not None:
+                    x, stats, i = y[0], None, y[1]
+                    continue
                 # bf16 payloads: the bf16-MFMA kernel, unless an eval-mode BatchNorm follows (the inference route is not moved)
                 eval_bn = i + 1 < n and isinstance(layers[i + 1], _BN_TYPES) and not layers[i + 1].training
                 y = bn_ops.plain_conv(x, layer, want_out_stats=feeds_bn, bf16_mfma=not eval_bn) \
@@ -134,6 +143,9 @@ class PointwiseSequential(nn.Sequential):
                             # inference: the same tail as one launch that never writes the conv's output (bn_ops.eval_mlp_plan)
                             y = bn_ops.bn_act_conv_maxpool_eval(x, layer, relu, layers[nxt], layers[nxt + 1], relu2,
                                                                 others=layers[i + 1:nxt] + layers[nxt + 2:n])
+                            if y is None and eval_steps:   # ... on the wide bf16 kernel (bn_ops.mlp_bf16_wide_plan)
+                                y = bn_ops.conv_bf16_wide(x, layers[nxt], layer, relu, layers[nxt + 1], relu2, pool=True,
+                                                          others=layers[i + 1:nxt] + layers[nxt + 2:n], in_stats=stats)
                         if y is not None:
                             return y, True
                 if nxt < n and _is_pointwise(layers[nxt]) and self.fuse_bn_conv:
@@ -145,6 +157,10 @@ class PointwiseSequential(nn.Sequential):
                     if y is not None:
                         x, stats = y if feeds_bn else (y, None)
                         i = nxt + 1
+                        continue
+                    y = self._wide_conv_step(x, layers, i, nxt, relu, pool_last, eval_steps, stats)
+                    if y is not None:
+                        x, stats, i = y[0], None, y[1]
                         continue
                 if pool_last and last and x.dim() == 4:
                     y = bn_ops.bn_act_maxpool(x, layer, relu, in_stats=stats)
@@ -161,6 +177,30 @@ class PointwiseSequential(nn.Sequential):
                 stats = None
                 i += 1
         return x, pooled
+
+    def _wide_conv_step(self, x, layers, bi, ci, relu, pool_last, eval_steps, stats):
+        """The conv layers[ci], with the BatchNorm layers[bi] [+ ReLU] in front of it (``bi`` None: it reads x), on the wide bf16
+        kernel (bn_ops.mlp_bf16_wide_plan) -> (y, index of the next layer), or None (the caller keeps its route).  Where an
+        eval-mode BatchNorm [+ ReLU] after the conv ends the MLP and no max follows, it goes into the store: one launch for the
+        tail.  Next to an eval-mode BatchNorm the step is part of the inference route: MLP_EVAL_FUSE switches it, and an MLP
+        whose group width the pooled store does not take keeps its route as a whole."""
+        from . import bn_ops
+        n, conv = len(layers), layers[ci]
+        bn = None if bi is None else layers[bi]
+        front = () if bi is None else tuple(layers[bi + 1:ci])
+        eval_next = ci + 1 < n and isinstance(layers[ci + 1], _BN_TYPES) and not layers[ci + 1].training
+        if ((bn is not None and not bn.training) or eval_next) and not (eval_steps and bn_ops.MLP_EVAL_FUSE):
+            return None
+        if eval_next and not pool_last:
+            relu2 = ci + 2 < n and isinstance(layers[ci + 2], nn.ReLU)
+            end = ci + (3 if relu2 else 2)
+            if end >= n:
+                y = bn_ops.conv_bf16_wide(x, conv, bn, relu, layers[ci + 1], relu2, others=front + tuple(layers[ci + 2:n]),
+                                          in_stats=stats)
+                if y is not None:
+                    return y, end
+        y = bn_ops.conv_bf16_wide(x, conv, bn, relu, others=front, in_stats=stats)
+        return None if y is None else (y, ci + 1)
 
     def forward(self, x):
         return self._run(x, False)[0]

@@ -147,10 +147,18 @@ class PointnetFPModule(nn.Module):
         c_known, c_skip = known_feats.shape[1], unknow_feats.shape[1]
         if conv.in_channels != c_known + c_skip or conv.out_channels > c_known or known_feats.dtype != unknow_feats.dtype:
             return None
-        w = conv.weight.view(conv.out_channels, conv.in_channels).to(known_feats.dtype)
+        from ..... import bn_ops
         b = known_feats.shape[0]
-        zf = torch.bmm(w[:, :c_known].unsqueeze(0).expand(b, -1, -1), known_feats)                 # (B, C_1, m)
-        zs = torch.bmm(w[:, c_known:].unsqueeze(0).expand(b, -1, -1), unknow_feats)               # (B, C_1, n)
+        # bf16 payloads without a gradient: each projection is one launch of the wide bf16 kernel on its column slice of the
+        # fp32 weight, read in place (bn_ops.mlp_bf16_wide_plan); the library GEMM otherwise
+        zf = bn_ops.conv_bf16_wide(known_feats, conv, cols=(0, c_known))                           # (B, C_1, m)
+        zs = bn_ops.conv_bf16_wide(unknow_feats, conv, cols=(c_known, c_known + c_skip))           # (B, C_1, n)
+        if zf is None or zs is None:
+            w = conv.weight.view(conv.out_channels, conv.in_channels).to(known_feats.dtype)
+        if zf is None:
+            zf = torch.bmm(w[:, :c_known].unsqueeze(0).expand(b, -1, -1), known_feats)
+        if zs is None:
+            zs = torch.bmm(w[:, c_known:].unsqueeze(0).expand(b, -1, -1), unknow_feats)
         z1 = pointnet2_utils.ThreeInterpolateAdd.apply(zf.contiguous(), idx, weight, zs.contiguous())
         return self.mlp._run(z1.unsqueeze(-1), False, start=1)[0].squeeze(-1)
 
