@@ -464,7 +464,12 @@ int mgar_pointwise_conv_fwd(const float *x, int B, int Cin, int P, const float *
  * layer's pre-BatchNorm input, B x Cin x P) and dy (gradient of the conv output): the kernel accumulates, on the matrix cores,
  * A[o][i] = sum dy m_i and B[o][i] = sum dy m_i xhat_i (m = ReLU mask, xhat = normalised x); then dW = gamma B + beta A,
  * dbeta_i = sum_o W A, dgamma_i = sum_o W B, coef = {dbeta, dgamma} / (B * P) for mgar_bn_act_bwd_apply.  Replaces
- * mgar_pointwise_conv_dw_act + the reduction pass of mgar_bn_act_bwd (8 * B * Cin * P bytes).  Cin, Cout <= 64. */
+ * mgar_pointwise_conv_dw_act + the reduction pass of mgar_bn_act_bwd (8 * B * Cin * P bytes).  Cin, Cout <= 64
+ * (MGAR_EUNSUPPORTED otherwise); B * P == 0 is MGAR_EINVAL (coef has no value for an empty batch).
+ * dw, dgamma and dbeta may each be NULL: that output is not written, the others and coef are unchanged by it.
+ * The ReLU mask is relu_nan's, !(pre <= 0) with the forward's pre-activation: a NaN pre-activation counts as active, so one
+ * NaN in x[., i, .] makes dw[:, i], dgamma[i] and coef[2i + 1] NaN -- what mgar_pointwise_conv_dw_act and autograd through
+ * BatchNorm -> ReLU -> conv give -- while dbeta[i] and coef[2i] stay finite (they count dy of that column). */
 int mgar_pointwise_dw_bnbwd_workspace_floats(int B, int Cin, int Cout, int P);
 int mgar_pointwise_conv_dw_bnbwd(const float *x, const float *dy, const float *w, int B, int Cin, int Cout, int P,
                                  const float *in_mean, const float *in_invstd, const float *in_gamma, const float *in_beta,

@@ -103,7 +103,9 @@ __global__ __launch_bounds__(256) void pointwise_dw_kernel(const float *__restri
     // pair mode: what a staged X element becomes (kind = second half of the virtual channels)
     auto pair_of = [&](float v, int r, bool kind) {
         const float mu = act_mu[r];
-        const bool on = !act.relu || (v - mu) * act_sc[r] + act_sh[r] > 0.f;      // the forward's expression, bit for bit
+        // the forward's expression, bit for bit, and relu_nan's compare: a NaN pre-activation counts as active, so it
+        // reaches B (NaN dW and dgamma, as mgar_pointwise_conv_dw_act gives) instead of dropping out of both sums
+        const bool on = !act.relu || !((v - mu) * act_sc[r] + act_sh[r] <= 0.f);
         return on ? (kind ? (v - mu) * act_is[r] : 1.f) : 0.f;
     };
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
