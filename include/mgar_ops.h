@@ -712,6 +712,17 @@ int mgar_dafm_attn_bwd(int S, int total_rows, int D, const int *scene_off, const
                        const float *v, const float *de, float sigma, float scale, const float *att,
                        const float *grad_out, float *gmat, float *grad_q, float *grad_k, float *grad_v,
                        void *stream);
+/* The same attention core with an ADDITIVE prior on the logits (FusionAttention, FusionAttention2 / 3,
+ * FusionAttention_gaussian of model/gat_model.py):
+ * Att = softmax(Q K^T * scale + P, dim=1), out = Att V.  prior: packed like de (block of scene s at de_off[s]),
+ * NULL = no prior.  Same layout, capacity (n_s <= MGAR_DAFM_MAX_N, enforced by the caller), D % 64 == 0, argument
+ * checks and early returns as mgar_dafm_attn_fwd.  NULL and a prior of zeros give the same bits. */
+int mgar_dafm_attn_add_fwd(int S, int total_rows, int D, const int *scene_off, const int *de_off, const float *q,
+                           const float *k, const float *v, const float *prior, float scale, float *att, float *out, void *stream);
+/* bwd: dL/d(QK^T) = dS * scale goes to gmat; the prior does not appear (it is added after the scaling and has no gradient). */
+int mgar_dafm_attn_add_bwd(int S, int total_rows, int D, const int *scene_off, const int *de_off, const float *q,
+                           const float *k, const float *v, float scale, const float *att, const float *grad_out,
+                           float *gmat, float *grad_q, float *grad_k, float *grad_v, void *stream);
 
 /* ===================== per-scene operations on PACKED scene rows (scenes of unequal actor counts) =====================
  * The rows of all S scenes are stacked; scene s owns rows [scene_off[s], scene_off[s+1]) and the dense (n_s, n_s) block at

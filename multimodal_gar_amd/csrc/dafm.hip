@@ -44,7 +44,12 @@ __device__ __forceinline__ float bcast_col(const float (&r)[DAFM_JPL], int j) {
     return __builtin_bit_cast(float, j < kWave ? lo : hi);
 }
 
+// ADD selects the prior on the logits (compile time):
+//   false : lg = dot * E * scale with E = softmax(-De / sigma) of the row -- FusionAttention_mat, the code as it always was;
+//   true  : lg = dot * scale + P, `de` holding the additive prior P packed like De, or NULL for none (FusionAttention,
+//           FusionAttention2 / 3, FusionAttention_gaussian); inv_sigma is unused and the E-softmax block is gone.
 // grid: ceil(total_rows / 4) workgroups of 4 waves
+template <bool ADD>
 __global__ __launch_bounds__(256) void dafm_fwd_kernel(int S, int total_rows, int D, const int *__restrict__ scene_off,
                                                        const int *__restrict__ de_off, const float *__restrict__ q,
                                                        const float *__restrict__ k, const float *__restrict__ v,
@@ -55,20 +60,29 @@ __global__ __launch_bounds__(256) void dafm_fwd_kernel(int S, int total_rows, in
     if (row >= total_rows) return;
     const int s = scene_of_row(row, S, scene_off);
     const int r0 = scene_off[s], n = scene_off[s + 1] - r0, i = row - r0;
-    const float *de_row = de + de_off[s] + (size_t)i * n;
+    const float *de_row = (ADD && de == nullptr) ? nullptr : de + de_off[s] + (size_t)i * n;
     float *att_row = att + de_off[s] + (size_t)i * n;
 
-    // ---- E row and raw logits, lanes along j ----
+    // ---- E row (or the additive prior's row) and raw logits, lanes along j ----
     float x[DAFM_JPL], dot[DAFM_JPL];
     float xmax = -__builtin_inff();
+    if constexpr (ADD) {
 #pragma unroll
-    for (int t = 0; t < DAFM_JPL; ++t) {
-        const int j = lane + t * kWave;
-        x[t] = j < n ? -(de_row[j] * inv_sigma) : -__builtin_inff();
-        xmax = fmaxf(xmax, x[t]);
-        dot[t] = 0.f;
+        for (int t = 0; t < DAFM_JPL; ++t) {
+            const int j = lane + t * kWave;
+            x[t] = (de_row != nullptr && j < n) ? de_row[j] : 0.f;  // no prior: the same add, of 0
+            dot[t] = 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < DAFM_JPL; ++t) {
+            const int j = lane + t * kWave;
+            x[t] = j < n ? -(de_row[j] * inv_sigma) : -__builtin_inff();
+            xmax = fmaxf(xmax, x[t]);
+            dot[t] = 0.f;
+        }
+        xmax = wave_max(xmax);
     }
-    xmax = wave_max(xmax);
     cfloat_p qi = (cfloat_p)(q + (size_t)row * D);
     for (int d0 = 0; d0 < D; d0 += 16) {
         float qc[16];
@@ -87,15 +101,23 @@ __global__ __launch_bounds__(256) void dafm_fwd_kernel(int S, int total_rows, in
             }
         }
     }
-    float esum = 0.f, ex[DAFM_JPL];
-#pragma unroll
-    for (int t = 0; t < DAFM_JPL; ++t) { ex[t] = (lane + t * kWave) < n ? __expf(x[t] - xmax) : 0.f; esum += ex[t]; }
-    esum = wave_sum(esum);
     float lg[DAFM_JPL], lmax = -__builtin_inff();
+    if constexpr (ADD) {
 #pragma unroll
-    for (int t = 0; t < DAFM_JPL; ++t) {
-        lg[t] = (lane + t * kWave) < n ? dot[t] * (ex[t] / esum) * scale : -__builtin_inff();
-        lmax = fmaxf(lmax, lg[t]);
+        for (int t = 0; t < DAFM_JPL; ++t) {
+            lg[t] = (lane + t * kWave) < n ? dot[t] * scale + x[t] : -__builtin_inff();
+            lmax = fmaxf(lmax, lg[t]);
+        }
+    } else {
+        float esum = 0.f, ex[DAFM_JPL];
+#pragma unroll
+        for (int t = 0; t < DAFM_JPL; ++t) { ex[t] = (lane + t * kWave) < n ? __expf(x[t] - xmax) : 0.f; esum += ex[t]; }
+        esum = wave_sum(esum);
+#pragma unroll
+        for (int t = 0; t < DAFM_JPL; ++t) {
+            lg[t] = (lane + t * kWave) < n ? dot[t] * (ex[t] / esum) * scale : -__builtin_inff();
+            lmax = fmaxf(lmax, lg[t]);
+        }
     }
     lmax = wave_max(lmax);
     float psum = 0.f, p[DAFM_JPL];
@@ -123,6 +145,9 @@ __global__ __launch_bounds__(256) void dafm_fwd_kernel(int S, int total_rows, in
 // Backward, pass A (one wave per query row i):
 //   dAtt_ij = gO_i . v_j ;  dS_ij = att_ij (dAtt_ij - sum_j' att_ij' dAtt_ij') ;
 //   G_ij = dS_ij * E_ij * scale  (= dL/d(q_i . k_j), written to gmat) ;  dq_i = sum_j G_ij k_j
+// ADD (see dafm_fwd_kernel): G_ij = dS_ij * scale -- the prior is added after the scaling and has no gradient, so `de` is
+// not read.
+template <bool ADD>
 __global__ __launch_bounds__(256) void dafm_bwd_rows_kernel(int S, int total_rows, int D, const int *__restrict__ scene_off,
                                                             const int *__restrict__ de_off, const float *__restrict__ k,
                                                             const float *__restrict__ v, const float *__restrict__ de,
@@ -135,21 +160,30 @@ __global__ __launch_bounds__(256) void dafm_bwd_rows_kernel(int S, int total_row
     const int s = scene_of_row(row, S, scene_off);
     const int r0 = scene_off[s], n = scene_off[s + 1] - r0, i = row - r0;
     const size_t mo = de_off[s] + (size_t)i * n;
-    float x[DAFM_JPL], a[DAFM_JPL], dot[DAFM_JPL];
-    float xmax = -__builtin_inff();
+    float a[DAFM_JPL], dot[DAFM_JPL];
+    float esum = 0.f, ex[DAFM_JPL];  // E of the row: !ADD only (read again where g is formed); dead code under ADD
+    if constexpr (ADD) {
 #pragma unroll
-    for (int t = 0; t < DAFM_JPL; ++t) {
-        const int j = lane + t * kWave;
-        x[t] = j < n ? -(de[mo + j] * inv_sigma) : -__builtin_inff();
-        a[t] = j < n ? att[mo + j] : 0.f;
-        xmax = fmaxf(xmax, x[t]);
-        dot[t] = 0.f;
+        for (int t = 0; t < DAFM_JPL; ++t) {
+            a[t] = (lane + t * kWave) < n ? att[mo + lane + t * kWave] : 0.f;
+            dot[t] = 0.f;
+        }
+    } else {
+        float x[DAFM_JPL];
+        float xmax = -__builtin_inff();
+#pragma unroll
+        for (int t = 0; t < DAFM_JPL; ++t) {
+            const int j = lane + t * kWave;
+            x[t] = j < n ? -(de[mo + j] * inv_sigma) : -__builtin_inff();
+            a[t] = j < n ? att[mo + j] : 0.f;
+            xmax = fmaxf(xmax, x[t]);
+            dot[t] = 0.f;
+        }
+        xmax = wave_max(xmax);
+#pragma unroll
+        for (int t = 0; t < DAFM_JPL; ++t) { ex[t] = (lane + t * kWave) < n ? __expf(x[t] - xmax) : 0.f; esum += ex[t]; }
+        esum = wave_sum(esum);
     }
-    xmax = wave_max(xmax);
-    float esum = 0.f, ex[DAFM_JPL];
-#pragma unroll
-    for (int t = 0; t < DAFM_JPL; ++t) { ex[t] = (lane + t * kWave) < n ? __expf(x[t] - xmax) : 0.f; esum += ex[t]; }
-    esum = wave_sum(esum);
     cfloat_p gi = (cfloat_p)(grad_out + (size_t)row * D);
     for (int d0 = 0; d0 < D; d0 += 16) {
         float gc[16];
@@ -175,7 +209,8 @@ __global__ __launch_bounds__(256) void dafm_bwd_rows_kernel(int S, int total_row
     float g[DAFM_JPL];
 #pragma unroll
     for (int t = 0; t < DAFM_JPL; ++t) {
-        g[t] = a[t] * (dot[t] - rsum) * (ex[t] / esum) * scale;
+        if constexpr (ADD) g[t] = a[t] * (dot[t] - rsum) * scale;
+        else g[t] = a[t] * (dot[t] - rsum) * (ex[t] / esum) * scale;
         if (lane + t * kWave < n) gmat[mo + lane + t * kWave] = g[t];
     }
     for (int d0 = lane * 4; d0 < D; d0 += 256) {
@@ -232,7 +267,7 @@ MGAR_API int mgar_dafm_attn_fwd(int S, int total_rows, int D, const int *scene_o
     // Att written (rows * n floats each, n = rows / S actors per scene); QK^T and Att V: 4 * rows * n * D flop
     const double n_avg = (double)total_rows / S;
     KtScope kt(KT_DAFM_FWD, (hipStream_t)stream, 4.0 * (4.0 * total_rows * D + 2.0 * total_rows * n_avg), 4.0 * total_rows * n_avg * D);
-    hipLaunchKernelGGL(dafm_fwd_kernel, dim3(ceil_div(total_rows, 4)), dim3(256), 0, (hipStream_t)stream, S, total_rows, D,
+    hipLaunchKernelGGL((dafm_fwd_kernel<false>), dim3(ceil_div(total_rows, 4)), dim3(256), 0, (hipStream_t)stream, S, total_rows, D,
                        scene_off, de_off, q, k, v, de, 1.0f / sigma, scale, att, out);
     return check_launch("dafm_attn_fwd: launch failed");
 }
@@ -252,9 +287,44 @@ MGAR_API int mgar_dafm_attn_bwd(int S, int total_rows, int D, const int *scene_o
     // dAtt = gO V^T, dq = dS K, dk = dS^T Q, dv = Att^T gO: 8 * rows * n * D flop
     const double n_avg = (double)total_rows / S;
     KtScope kt(KT_DAFM_BWD, (hipStream_t)stream, 4.0 * (7.0 * total_rows * D + 4.0 * total_rows * n_avg), 8.0 * total_rows * n_avg * D);
-    hipLaunchKernelGGL(dafm_bwd_rows_kernel, dim3(ceil_div(total_rows, 4)), dim3(256), 0, (hipStream_t)stream, S, total_rows,
+    hipLaunchKernelGGL((dafm_bwd_rows_kernel<false>), dim3(ceil_div(total_rows, 4)), dim3(256), 0, (hipStream_t)stream, S, total_rows,
                        D, scene_off, de_off, k, v, de, 1.0f / sigma, scale, att, grad_out, gmat, grad_q);
     hipLaunchKernelGGL(dafm_bwd_cols_kernel, dim3(ceil_div(total_rows, 4)), dim3(256), 0, (hipStream_t)stream, S, total_rows,
                        D, scene_off, de_off, q, att, grad_out, gmat, grad_k, grad_v);
     return check_launch("dafm_attn_bwd: launch failed");
+}
+
+MGAR_API int mgar_dafm_attn_add_fwd(int S, int total_rows, int D, const int *scene_off,
+                                    const int *de_off, const float *q, const float *k,
+                                    const float *v, const float *prior, float scale,
+                                    float *att, float *out, void *stream) {
+    MGAR_REQUIRE(S >= 0 && total_rows >= 0 && D > 0 && D % 64 == 0, "dafm_attn_add_fwd: bad sizes (D must be a multiple of 64)");
+    if (S == 0 || total_rows == 0) return MGAR_OK;
+    MGAR_REQUIRE(scene_off && de_off && q && k && v && att && out, "dafm_attn_add_fwd: null pointer");
+    // as mgar_dafm_attn_fwd, the prior (where there is one) in De's place
+    const double n_avg = (double)total_rows / S;
+    KtScope kt(KT_DAFM_FWD, (hipStream_t)stream, 4.0 * (4.0 * total_rows * D + (prior ? 2.0 : 1.0) * total_rows * n_avg),
+               4.0 * total_rows * n_avg * D);
+    hipLaunchKernelGGL((dafm_fwd_kernel<true>), dim3(ceil_div(total_rows, 4)), dim3(256), 0, (hipStream_t)stream, S, total_rows,
+                       D, scene_off, de_off, q, k, v, prior, 0.f, scale, att, out);
+    return check_launch("dafm_attn_add_fwd: launch failed");
+}
+
+MGAR_API int mgar_dafm_attn_add_bwd(int S, int total_rows, int D, const int *scene_off,
+                                    const int *de_off, const float *q, const float *k,
+                                    const float *v, float scale, const float *att,
+                                    const float *grad_out, float *gmat, float *grad_q,
+                                    float *grad_k, float *grad_v, void *stream) {
+    MGAR_REQUIRE(S >= 0 && total_rows >= 0 && D > 0 && D % 64 == 0, "dafm_attn_add_bwd: bad sizes (D must be a multiple of 64)");
+    if (S == 0 || total_rows == 0) return MGAR_OK;
+    MGAR_REQUIRE(scene_off && de_off && q && k && v && att && grad_out && gmat && grad_q && grad_k && grad_v,
+                 "dafm_attn_add_bwd: null pointer");
+    // as mgar_dafm_attn_bwd without the read of De: Att read + the (rows, n) scratch written and read
+    const double n_avg = (double)total_rows / S;
+    KtScope kt(KT_DAFM_BWD, (hipStream_t)stream, 4.0 * (7.0 * total_rows * D + 3.0 * total_rows * n_avg), 8.0 * total_rows * n_avg * D);
+    hipLaunchKernelGGL((dafm_bwd_rows_kernel<true>), dim3(ceil_div(total_rows, 4)), dim3(256), 0, (hipStream_t)stream, S,
+                       total_rows, D, scene_off, de_off, k, v, nullptr, 0.f, scale, att, grad_out, gmat, grad_q);
+    hipLaunchKernelGGL(dafm_bwd_cols_kernel, dim3(ceil_div(total_rows, 4)), dim3(256), 0, (hipStream_t)stream, S, total_rows,
+                       D, scene_off, de_off, q, att, grad_out, gmat, grad_k, grad_v);
+    return check_launch("dafm_attn_add_bwd: launch failed");
 }

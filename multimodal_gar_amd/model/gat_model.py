@@ -19,7 +19,8 @@ What runs where:
 of the batch has the same number of actors and the configuration is the shipped one
 (Multimodal_cfg/mil3.yaml: FUSION Attention_mat, cosine similarity, EUCLIDEAN) it takes a
 batched route that evaluates all scenes in one pass -- same arithmetic, no Python loop, no
-host synchronisation -- and is tested against the per-scene route.
+host synchronisation -- and is tested against the per-scene route.  The packed form of that
+route (forward_packed: any actor counts) also serves the FUSION values of _PACKED_FUSIONS.
 """
 import math
 import os
@@ -33,7 +34,7 @@ from .backbone import InceptionI3d, NLBlockND
 from .. import vision_ops as TO
 from .. import graph_ops as pyg_nn
 from ..metric_ops import pairwise_cosine_similarity, pairwise_euclidean_distance
-from ..dafm_ops import dafm_attention, scene_offsets
+from ..dafm_ops import dafm_attention, dafm_attention_add, scene_offsets
 from ..scene_ops import scene_batch_norm, scene_gram, scene_layout, scene_pair_geometry
 from ..pcdet.models import build_network, load_data_to_gpu
 
@@ -136,6 +137,29 @@ class _TwoBranchFusion(nn.Module):
     def forward(self, R, L, Dg, De):
         return self.branches(R, L, Dg, De)
 
+    def forward_stacked(self, R, L, de_flat, dg_flat, scene_off, de_off, pairs=None):
+        """`branches` for the rows of all scenes at once: R, L (sum_s n_s, D); de_flat, dg_flat: the scenes' (n_s, n_s)
+        matrices flattened and concatenated (None where the variant reads neither).  The priors are element-wise, so the
+        per-scene formulas apply to the flat tensors as they are; the attention core is the fused HIP kernel with an
+        additive prior (csrc/dafm.hip).  pairs: sum_s n_s^2 as a host int (scene_layout().pairs); without it the offsets are
+        read back from the device (dafm_attention_add).  -> (R', L').
+        NOTE: FusionAttention_mat.forward_stacked, which is older, takes (R, L, de_flat, scene_off, de_off) -- no dg_flat;
+        GAR_Fusion_Net3._fuse_packed is the one caller and tells them apart by cfg.FUSION.  This method serves the variants
+        routed there (FusionAttention, FusionAttention2 / 3, FusionAttention_gaussian); FusionAttention_cat / _sum inherit
+        it and get the plain pair (R', L'), not their own combination, and the positional variant is refused below."""
+        if self.q_extra:
+            raise NotImplementedError("%s: no stacked route (its queries and keys take extra columns)" % type(self).__name__)
+        scale = 1.0 / self.out_dim ** 0.5
+        kind_r, E_r = self.prior_r(dg_flat, de_flat)
+        kind_l, E_l = self.prior_l(dg_flat, de_flat, E_r)
+        if 'mul' in (kind_r, kind_l):
+            raise NotImplementedError("%s: no stacked route for a multiplicative prior" % type(self).__name__)
+        att_r, _ = dafm_attention_add(L @ self.WQ_r, R @ self.WK_r, R @ self.WV_r, E_r, scene_off, de_off, scale, pairs)
+        R_prime = self._post("r", att_r, R)
+        att_l, _ = dafm_attention_add(R @ self.WQ_l, L @ self.WK_l, L @ self.WV_l, E_l, scene_off, de_off, scale, pairs)
+        L_prime = self._post("l", att_l, L)
+        return R_prime, L_prime
+
 
 class FusionAttention(_TwoBranchFusion):
     """Plain cross attention, no prior (reference :77-156)."""
@@ -157,6 +181,9 @@ class FusionAttention2(FusionAttention3):
     def forward(self, R, L, Dg, De):
         Rp, Lp = self.branches(R, L, Dg, De)
         return torch.max(torch.stack((Rp, Lp)), dim=0)[0]
+
+    def forward_stacked(self, R, L, de_flat, dg_flat, scene_off, de_off, pairs=None):
+        return torch.max(*super().forward_stacked(R, L, de_flat, dg_flat, scene_off, de_off, pairs))
 
 
 class FusionAttention_cat(FusionAttention3):
@@ -388,6 +415,10 @@ class Actionhead(nn.Module):
         return tuple(getattr(self, name)(x) for name, _, _ in _HEAD_SPECS)
 
 
+# FUSION values whose scenes can be evaluated together on packed rows (forward_packed); the rest goes scene by scene
+_PACKED_FUSIONS = ('Attention_mat', 'sum', 'Attention_normal', 'Attention_max', 'Attention_multi', 'Attention_gaussian')
+
+
 class GAR_Fusion_Net3(nn.Module):
     def __init__(self, cfg) -> None:
         super().__init__()
@@ -564,7 +595,7 @@ class GAR_Fusion_Net3(nn.Module):
         counts = self._scene_counts(RGB_feature, LiDAR_feature, person_id)
         if counts is None:
             return self.forward_per_scene(RGB_feature, LiDAR_feature, bboxes, bboxes3d, social_group_id, person_id)
-        if all(c == counts[0] for c in counts):
+        if self.cfg.FUSION == 'Attention_mat' and all(c == counts[0] for c in counts):
             return self._forward_batched(RGB_feature, LiDAR_feature, bboxes, bboxes3d, person_id, counts[0])
         return self._forward_ragged(RGB_feature, LiDAR_feature, bboxes, bboxes3d, counts)
 
@@ -616,12 +647,14 @@ class GAR_Fusion_Net3(nn.Module):
 
     # ------------------------------------------------------------------ batched route
     def _scene_counts(self, RGB_feature, LiDAR_feature, person_id):
-        """Actors per scene (host ints) when the batch can take a batched route -- _forward_batched for equal counts,
-        _forward_ragged otherwise -- and None when it goes scene by scene: another configuration than the shipped one, valid
+        """Actors per scene (host ints) when the batch can take a batched route -- _forward_batched for equal counts under
+        Attention_mat, _forward_ragged otherwise -- and None when it goes scene by scene: a configuration outside
+        _scene_counts_ok (the shipped one and the other FUSION values of _PACKED_FUSIONS pass), valid
         slots that are not the leading columns, a scene of fewer than 2 (BatchNorm1d raises there, and so does the per-scene
         route) or more than MGAR_DAFM_MAX_N actors, or an empty batch.  The caller can promise the counts and spare the host
         read: `uniform_actor_count` (one int for every scene) or `actor_counts` (a sequence of host ints, one per scene); where
-        both are set, `uniform_actor_count` is the one that holds."""
+        both are set, `uniform_actor_count` is the one that holds.  A promised count is taken as given: a caller that promises
+        as many actors as there are slots gets them all, where the derived count of such a scene is one short (below)."""
         if RGB_feature is None or LiDAR_feature is None or not self._scene_counts_ok([2]):
             return None
         S, MNP = person_id.shape
@@ -640,6 +673,9 @@ class GAR_Fusion_Net3(nn.Module):
             valid = person_id >= 0
             cnt = valid.sum(dim=1)
             leading = (valid == (torch.arange(MNP, device=person_id.device)[None, :] < cnt[:, None])).all()
+            # a scene without a single -1 slot: the reference counts len(unique(person_id)) - 1 (get_num_person), one actor
+            # short, and so does the per-scene route; the last slot is dropped here too
+            cnt = cnt - (cnt == MNP).to(cnt.dtype)
             host = torch.cat((cnt, leading.view(1).to(cnt.dtype))).tolist()
             if not host[-1]:
                 return None
@@ -651,7 +687,7 @@ class GAR_Fusion_Net3(nn.Module):
     def _scene_counts_ok(self, counts):
         """Whether scenes of these actor counts can take a batched route under this configuration."""
         cfg = self.cfg
-        ok = (cfg.MODALITY == 'Multi' and cfg.FUSION == 'Attention_mat' and cfg.sim == 'cosine' and cfg.FEAT_NORM
+        ok = (cfg.MODALITY == 'Multi' and cfg.FUSION in _PACKED_FUSIONS and cfg.sim == 'cosine' and cfg.FEAT_NORM
               and cfg.get("ind_action_concat") and not cfg.get("sg_feat_org") and not cfg.get("Social_Layer")
               and not cfg.get("Social_Encoder") and not cfg.get("Action_concat") and not cfg.get("DISABLE_BATCHED"))
         return bool(ok) and len(counts) > 0 and min(counts) >= 2 and max(counts) <= 128
@@ -731,6 +767,32 @@ class GAR_Fusion_Net3(nn.Module):
         return scene_batch_norm(x, bn.weight, bn.bias, scene_off, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                 bn.eps, bn.momentum)
 
+    def _fuse_packed(self, R, L, de, dg, so, do, pairs=None):
+        """`_fuse` for the packed rows of all scenes (the configurations of _PACKED_FUSIONS): de, dg are the scenes' flat
+        (n_s, n_s) matrices, so / do their offsets, pairs = sum n_s^2 (host int; None: read back from the device)."""
+        fus = self.cfg.FUSION
+        if fus == 'Attention_mat':
+            Rp, Lp = self.AttFusModule1.forward_stacked(R, L, de, so, do)
+            Rp, Lp = self.AttFusModule2.forward_stacked(Rp, Lp, de, so, do)
+            return torch.max(Rp, Lp)
+        if fus == 'sum':
+            return R + L
+        if fus == 'Attention_normal':
+            # module 2 on the ORIGINAL R, L (reference :1453); module 1's result is discarded there, so it is not
+            # evaluated here and its parameters stay without a gradient, as on the per-scene route
+            return torch.max(*self.AttFusModule2.forward_stacked(R, L, None, None, so, do, pairs))
+        if fus == 'Attention_max':
+            return self.AttFusModule.forward_stacked(R, L, de, dg, so, do, pairs)
+        if fus == 'Attention_multi':
+            Rp, Lp = self.AttFusModule1.forward_stacked(R, L, de, dg, so, do, pairs)
+            return self.AttFusModule2.forward_stacked(Rp, Lp, de, dg, so, do, pairs)
+        if fus == 'Attention_gaussian':
+            Rp, Lp = R, L
+            for i in range(4):
+                Rp, Lp = getattr(self, "AttFusModule%d" % (i + 1)).forward_stacked(Rp, Lp, de, dg, so, do, pairs)
+            return torch.max(Rp, Lp)
+        raise NotImplementedError("GAR_MODEL.FUSION = %r has no packed route" % fus)
+
     def forward_packed(self, R, L, bb, ctr, counts, MNP):
         """R, L (rows, 512), bb (rows, 4) xyxy, ctr (rows, 3): the rows of all scenes stacked, scene s holding counts[s] of
         them (host ints, each 2..MGAR_DAFM_MAX_N) -> the 16 zero-padded (S, MNP, .) tensors of forward().  Every step is one
@@ -741,9 +803,7 @@ class GAR_Fusion_Net3(nn.Module):
         R = self._packed_bn(self.bn_rgb, R, so)
         L = self._packed_bn(self.bn_lidar, L, so)
         de, dg = scene_pair_geometry(ctr, bb, so, do, lay.pairs)
-        Rp, Lp = self.AttFusModule1.forward_stacked(R, L, de, so, do)
-        Rp, Lp = self.AttFusModule2.forward_stacked(Rp, Lp, de, so, do)
-        fused = torch.max(Rp, Lp)
+        fused = self._fuse_packed(R, L, de, dg, so, do, lay.pairs)
         fn = fused / fused.norm(dim=1, keepdim=True)
         Dv = scene_gram(fn, so, do, lay.pairs)
         A_theta = self.D_embed(torch.stack((Dv, dg), dim=-1)).reshape(-1)                        # (sum n_s^2,)

@@ -67,8 +67,10 @@ def lidar_model_cfg(n_points, route="pointnet2"):
     raise ValueError(route)
 
 
-def model_cfg(n_actors, n_points, gat=True, route="pointnet2"):
-    """The shipped configuration (Multimodal_cfg/mil3.yaml) with the synthetic sizes plugged in.
+def model_cfg(n_actors, n_points, gat=True, route="pointnet2", fusion="Attention_mat"):
+    """The shipped configuration (Multimodal_cfg/mil3.yaml) with the synthetic sizes plugged in.  fusion: GAR_MODEL.FUSION, the
+    shipped DAFM by default; the ablation variants with fixed sigmas (Attention_multi, Attention_gaussian) take them from
+    their classes, SIGMA is for the others.
     GAT_module is False in the shipped YAML (:86); the north-star includes the GAT path, so the
     benchmark flips it on (SURVEY.md "facts")."""
     return EasyDict(
@@ -76,7 +78,7 @@ def model_cfg(n_actors, n_points, gat=True, route="pointnet2"):
         RGB_BACKBONE=dict(I3D_FREEZE=True, EMBEDDING_DIM=512, INTER_PERSON=False, GAT_module=bool(gat), two_stage_att=False),
         LiDAR_BACKBONE=dict(CLASS_NAMES=["Pedestrian"], MODEL=lidar_model_cfg(n_points, route),
                             SELF_ATT1=dict(USE=True, DIM=3, INTER_PERSON=False), two_stage_att=False),
-        GAR_MODEL=dict(MODALITY="Multi", FUSION="Attention_mat", SIGMA=10, FEAT_NORM=True, EUCLIDEAN=True,
+        GAR_MODEL=dict(MODALITY="Multi", FUSION=fusion, SIGMA=10, FEAT_NORM=True, EUCLIDEAN=True,
                        ind_action_concat=True, sg_feat_org=False, FEATURE_DIM=1024, HIDDEN_DIM=512, sim="cosine"))
 
 
@@ -136,10 +138,10 @@ def make_batch(seed, n_clips, n_frames, n_actors, n_points, height, width, devic
 class ClipModel(nn.Module):
     """GAR_Fusion_ALL plus the clip/frame plumbing described in the module docstring."""
 
-    def __init__(self, n_actors, n_points, gat=True, route="pointnet2"):
+    def __init__(self, n_actors, n_points, gat=True, route="pointnet2", fusion="Attention_mat"):
         super().__init__()
         from .model.gat_model import GAR_Fusion_ALL
-        self.cfg = model_cfg(n_actors, n_points, gat, route)
+        self.cfg = model_cfg(n_actors, n_points, gat, route, fusion)
         self.route = route
         self.n_actors = n_actors
         self.dataset = SyntheticDataset()
@@ -556,11 +558,11 @@ class TrainStep(_GraphStep):
     (no DDP wrapper: its hooks cannot live inside a captured backward), then Adam."""
 
     def __init__(self, n_actors, n_points, device, gat=True, route="pointnet2", ddp=False, lr=1e-3, seed=2023,
-                 manual_allreduce=False, loss="reference"):
+                 manual_allreduce=False, loss="reference", fusion="Attention_mat"):
         assert loss in ("reference", "synthetic")
         self.loss_kind = loss
         torch.manual_seed(seed)  # the reference seeds 2023 (train_func.py:45-47)
-        self.model = ClipModel(n_actors, n_points, gat, route).to(device)
+        self.model = ClipModel(n_actors, n_points, gat, route, fusion).to(device)
         self.model.train()
         self.module = self.model
         self.manual_allreduce = bool(manual_allreduce)
@@ -676,10 +678,11 @@ class ForwardStep(_GraphStep):
     and the per-scene fusion net stay fp32 / int32 (SURVEY.md section 8 header), so every index tensor is bit-identical to
     the fp32 run.  Same interface as TrainStep (capture / run / run_eager, .module, .graph)."""
 
-    def __init__(self, n_actors, n_points, device, gat=True, route="pointnet2", precision="fp32", seed=2023):
+    def __init__(self, n_actors, n_points, device, gat=True, route="pointnet2", precision="fp32", seed=2023,
+                 fusion="Attention_mat"):
         assert precision in ("fp32", "bf16")
         torch.manual_seed(seed)
-        self.model = ClipModel(n_actors, n_points, gat, route).to(device)
+        self.model = ClipModel(n_actors, n_points, gat, route, fusion).to(device)
         self.model.train()
         self.module = self.model
         self.precision = precision
