@@ -656,7 +656,7 @@ int mgar_conv3d_k3_bf16_fwd_affine(const void *x, int N, int Cin, int D, int H, 
                                    void *stream);
 
 /* The 1x1x1 units of Inception-I3D (model/backbone.py:134-206 with kernel_shape [1, 1, 1]: ``Conv3d_2b_1x1`` and four units per
- * InceptionModule) for bf16 payloads on the bf16 MFMA (csrc/conv1x1_bf16.hip; ABI 22; forward only): per sample the product
+ * InceptionModule) for bf16 payloads on the bf16 MFMA (csrc/pointwise_wide_bf16.hip; ABI 22; forward only): per sample the product
  * Y[n] (Cout, P) = W (Cout, Cin) . X[n] (Cin, P), P = T * H * W, on the NCDHW tensor as it lies.  x (N, Cin, P) bf16 contiguous;
  * w (Cout, Cin) fp32 row-major (the master weight, or a bf16 weight widened exactly); element (n, o, p) of y (bf16) lies at
  * y + n * y_batch_stride + o * P + p, so y may be the channel slice Y[:, c0 : c0 + Cout] of a wider contiguous NCDHW tensor.

@@ -33,10 +33,6 @@
 
 namespace mgar {
 
-typedef float __attribute__((ext_vector_type(16))) f32x16;
-typedef __bf16 __attribute__((ext_vector_type(8))) bf16x8;
-typedef unsigned int __attribute__((ext_vector_type(4))) u32x4;
-
 constexpr int CB_CG = 64;                              // output channels per workgroup (2 MFMA row blocks)
 constexpr int CB_CI = 8;                               // input channels per group (the k of one item)
 constexpr int CB_STEPS = 14;                           // MFMA k-steps per group: 27 taps + one zero item

@@ -22,6 +22,38 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {   // one v
 __device__ __forceinline__ float bf16_lo(uint32_t u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 
+// operand types of v_mfma_f32_32x32x16_bf16: the accumulator, an A / B fragment, and the fragment as the four dwords it is packed in
+typedef float __attribute__((ext_vector_type(16))) f32x16;
+typedef __bf16 __attribute__((ext_vector_type(8))) bf16x8;
+typedef unsigned int __attribute__((ext_vector_type(4))) u32x4;
+
+// The B fragments of the point-wise bf16 kernels (csrc/pointwise_bf16.hip, csrc/pointwise_wide_bf16.hip) for an identity
+// prologue: load j of a lane holds channel j of columns 4 l .. 4 l + 3, fragment i wants column 4 l + i of channels 0 .. 7 --
+// dword d of a fragment = channels 2 d (low half), 2 d + 1 (high half).  16-bit selects, nothing is rounded.
+__device__ __forceinline__ void pack_b_fragments(const uint2 (&buf)[8], u32x4 (&bf)[4]) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const uint2 u0 = buf[2 * d], u1 = buf[2 * d + 1];
+        bf[0][d] = (u0.x & 0xffffu) | (u1.x << 16);
+        bf[1][d] = (u0.x >> 16) | (u1.x & 0xffff0000u);
+        bf[2][d] = (u0.y & 0xffffu) | (u1.y << 16);
+        bf[3][d] = (u0.y >> 16) | (u1.y & 0xffff0000u);
+    }
+}
+
+// Channel ch's entry (sc, beta, mean, -) of the same kernels' BatchNorm prologue table, act(v) = ((v - mean) * sc) + beta with
+// sc = invstd * gamma; gamma / beta NULL = 1 / 0.  A padding channel (ch >= Cin) gets (1, 0, 0): (0 - 0) * 1 + 0 = +0.
+__device__ __forceinline__ float4 bn_prologue_entry(int ch, int Cin, const float *mean, const float *invstd, const float *gamma,
+                                                    const float *beta) {
+    float sc = 1.f, sh = 0.f, mu = 0.f;
+    if (ch < Cin) {
+        sc = invstd[ch] * (gamma ? gamma[ch] : 1.f);
+        sh = beta ? beta[ch] : 0.f;
+        mu = mean[ch];
+    }
+    return make_float4(sc, sh, mu, 0.f);
+}
+
 template <typename T> struct Payload;
 
 template <> struct Payload<float> {

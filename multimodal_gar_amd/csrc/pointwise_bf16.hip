@@ -30,10 +30,6 @@
 
 namespace mgar {
 
-typedef float __attribute__((ext_vector_type(16))) f32x16;
-typedef __bf16 __attribute__((ext_vector_type(8))) bf16x8;
-typedef unsigned int __attribute__((ext_vector_type(4))) u32x4;
-
 constexpr int PB_COLS = 128;   // columns per wave tile: 4 interleaved sub-tiles of 32
 constexpr int PB_KC = 16;      // channels per k-step (one MFMA per sub-tile and row block)
 
@@ -65,15 +61,8 @@ __global__ __launch_bounds__(256, 2) void pointwise_bf16_kernel(PbArgs a) {
         wl[e] = u32x4{pack_bf16x2(wv[0], wv[1]), pack_bf16x2(wv[2], wv[3]), pack_bf16x2(wv[4], wv[5]), pack_bf16x2(wv[6], wv[7])};
     }
     if constexpr (ACT) {
-        for (int ch = threadIdx.x; ch < nks * PB_KC; ch += 256) {
-            float sc = 1.f, sh = 0.f, mu = 0.f;   // padding channels: (0 - 0) * 1 + 0 = +0
-            if (ch < a.Cin) {
-                sc = a.invstd[ch] * (a.gamma ? a.gamma[ch] : 1.f);
-                sh = a.beta ? a.beta[ch] : 0.f;
-                mu = a.mean[ch];
-            }
-            act[ch] = make_float4(sc, sh, mu, 0.f);
-        }
+        for (int ch = threadIdx.x; ch < nks * PB_KC; ch += 256)
+            act[ch] = bn_prologue_entry(ch, a.Cin, a.mean, a.invstd, a.gamma, a.beta);
     }
     __syncthreads();
 
@@ -136,14 +125,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_bf16_kernel(PbArgs a) {
                 for (int i = 0; i < 4; ++i) bf[i][d] = pack_bf16x2(v[0][i], v[1][i]);
             }
         } else {
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                const uint2 u0 = buf[2 * d], u1 = buf[2 * d + 1];
-                bf[0][d] = (u0.x & 0xffffu) | (u1.x << 16);
-                bf[1][d] = (u0.x >> 16) | (u1.x & 0xffff0000u);
-                bf[2][d] = (u0.y & 0xffffu) | (u1.y << 16);
-                bf[3][d] = (u0.y >> 16) | (u1.y & 0xffff0000u);
-            }
+            pack_b_fragments(buf, bf);
         }
 #pragma unroll
         for (int ob = 0; ob < OB; ++ob) {

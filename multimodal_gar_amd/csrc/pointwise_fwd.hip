@@ -43,8 +43,6 @@
 
 namespace mgar {
 
-typedef float __attribute__((ext_vector_type(16))) f32x16;
-
 constexpr int PF_COLS = 128;  // columns per wave tile
 // channels per slab (2 per MFMA k-step): 16, or 8 for the 64-output-channel instance so that its 128 accumulator
 // registers + two slab buffers stay under 256 VGPRs (2 waves per SIMD instead of 1)

@@ -23,10 +23,6 @@
 
 namespace mgar {
 
-typedef float __attribute__((ext_vector_type(16))) f32x16;
-typedef __bf16 __attribute__((ext_vector_type(8))) bf16x8;
-typedef unsigned int __attribute__((ext_vector_type(4))) u32x4;
-
 constexpr int SB_MAXC = 128;      // C_in, C_out <= 128
 constexpr int SB_MAXK = 343;      // kernel offsets (7 x 7 x 7)
 constexpr int SB_ROWS = 128;      // output rows per workgroup: 4 waves x 32

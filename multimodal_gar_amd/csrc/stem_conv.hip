@@ -25,8 +25,6 @@
 
 namespace mgar {
 
-typedef float __attribute__((ext_vector_type(16))) f32x16;
-
 constexpr int SCV_K = 7, SCV_S = 2, SCV_CIN = 3, SCV_COUT = 64;
 constexpr int SCV_TH = 8, SCV_TW = 32;                                   // output tile (ho x wo) per workgroup
 constexpr int SCV_IH = SCV_S * (SCV_TH - 1) + SCV_K;                      // 21 input rows
@@ -196,8 +194,6 @@ __global__ void stem_pack_weights_kernel(const float *__restrict__ w, float *__r
 // its A fragment 16 contiguous bytes of the weights packed [k-step][co][kh parity][kw].  A (kt, c_in) slab is 4 k-steps (kh pairs
 // (0,1) (2,3) (4,5) (6,-)) x 4 accumulators = 16 MFMAs per wave instead of 100 fp32 ones; same tile, same double-buffered
 // pipeline, same epilogue.  Weights are rounded to bf16 once per call (what a bf16 convolution does).
-typedef __bf16 __attribute__((ext_vector_type(8))) bf16x8;
-typedef unsigned int __attribute__((ext_vector_type(4))) u32x4;
 constexpr int SCB_COLS = 72;                                              // patch row pitch in bf16 (69 columns + pad)
 constexpr int SCB_IN_HALVES = SCV_IH * SCB_COLS;                          // 1512
 constexpr int SCB_W_HALVES = 4 * SCV_COUT * 16;                           // 4096 per slab: [step][co][h][8]

@@ -191,7 +191,7 @@ class Unit3D(nn.Module):
         L.call("mgar_conv3d_k3_fwd", L.fptr(x), n, cin, d, h, w, L.fptr(wf), c.out_channels, L.fptr(wp), L.fptr(y), L.stream_of(x))
         return y
 
-    k1_bf16 = os.environ.get("MGAR_I3D_K1_BF16", "0") != "0"          # 1x1x1 units on bf16 payloads: csrc/conv1x1_bf16.hip (bf16 MFMA, one launch for all samples) instead of the per-sample library GEMMs; inside gemm_1x1.  Off by default: c2's step did not clear the bar
+    k1_bf16 = os.environ.get("MGAR_I3D_K1_BF16", "0") != "0"          # 1x1x1 units on bf16 payloads: mgar_conv1x1_bf16_fwd of csrc/pointwise_wide_bf16.hip (bf16 MFMA, one launch for all samples) instead of the per-sample library GEMMs; inside gemm_1x1.  Off by default: c2's step did not clear the bar
 
     K1_MAX_IN, K1_MAX_OUT = 1024, 512                                   # mgar_conv1x1_bf16_fwd's channel range
 
@@ -220,7 +220,7 @@ class Unit3D(nn.Module):
         return cached[1]
 
     def _k1_conv_bf16(self, x):
-        """bf16 payloads (autocast on or off): the unit as ONE launch of csrc/conv1x1_bf16.hip for all samples, bf16 NCDHW in and
+        """bf16 payloads (autocast on or off): the unit as ONE launch of mgar_conv1x1_bf16_fwd[_affine] (csrc/pointwise_wide_bf16.hip) for all samples, bf16 NCDHW in and
         out, the weight as in _k3_conv_bf16.  Or None."""
         if not self._k1_bf16_route(x):
             return None

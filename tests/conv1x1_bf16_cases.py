@@ -1,5 +1,5 @@
 """Cases, operands, float64 reference and bounds shared by tests/test_conv1x1_bf16_cpu.py and tests/test_conv1x1_bf16_gpu.py for
-mgar_conv1x1_bf16_fwd / mgar_conv1x1_bf16_fwd_affine (csrc/conv1x1_bf16.hip).
+mgar_conv1x1_bf16_fwd / mgar_conv1x1_bf16_fwd_affine (csrc/pointwise_wide_bf16.hip).
 
 The kernel's contract (include/mgar_ops.h):
     w~[o,i]    = bf16(w[o,i])

@@ -1,4 +1,4 @@
-"""mgar_conv1x1_bf16_fwd / mgar_conv1x1_bf16_fwd_affine (csrc/conv1x1_bf16.hip) without a device: the ABI surface, the bounds of
+"""mgar_conv1x1_bf16_fwd / mgar_conv1x1_bf16_fwd_affine (csrc/pointwise_wide_bf16.hip) without a device: the ABI surface, the bounds of
 tests/conv1x1_bf16_cases.py pinned as satisfiable (fp32 restatements of the kernel in two k-step orders lie inside them) and as
 sharp (wrong restatements leave them), Unit3D's routing predicates on attribute stand-ins, and the weight cache."""
 import ctypes
@@ -44,8 +44,8 @@ def test_library_exports_the_symbols_and_abi_22():
     names = [_lib.raw("mgar_ktimer_name", i).decode() for i in range(_lib.raw("mgar_ktimer_count"))]
     assert "conv1x1_bf16_kernel" in names and names[-1] != "conv1x1_bf16_kernel" and len(set(names)) == len(names)
     assert names[-1] == "voxel_roi_pool_eval"
-    assert op_timer.KERNEL_SOURCES.get("conv1x1_bf16_kernel") == "conv1x1_bf16.hip"
-    assert os.path.exists(os.path.join(ROOT, "multimodal_gar_amd", "csrc", "conv1x1_bf16.hip"))
+    assert op_timer.KERNEL_SOURCES.get("conv1x1_bf16_kernel") == "pointwise_wide_bf16.hip"
+    assert os.path.exists(os.path.join(ROOT, "multimodal_gar_amd", "csrc", "pointwise_wide_bf16.hip"))
 
 
 def test_case_list_is_the_issues():

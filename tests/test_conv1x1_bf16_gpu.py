@@ -1,4 +1,4 @@
-"""csrc/conv1x1_bf16.hip on the device: mgar_conv1x1_bf16_fwd and mgar_conv1x1_bf16_fwd_affine against the float64 references and
+"""The I3D entry points of csrc/pointwise_wide_bf16.hip on the device: mgar_conv1x1_bf16_fwd and mgar_conv1x1_bf16_fwd_affine against the float64 references and
 the bounds of tests/conv1x1_bf16_cases.py, a strided channel-slice destination, batch independence, repeatability, non-finite
 values and the refusals; then the routing of Unit3D / InceptionModule / InceptionI3d for bf16 payloads in train and eval mode."""
 import copy

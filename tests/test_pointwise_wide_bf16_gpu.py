@@ -1,7 +1,8 @@
 """csrc/pointwise_wide_bf16.hip on the device: mgar_pointwise_wide_bf16_fwd / mgar_pointwise_wide_maxpool_bf16_fwd against the
 float64 reference of tests/pointwise_wide_bf16_cases.py on the ROUNDED operands (per-element bounds: any fp32 accumulation order,
 the one fma of the affine store, one bf16 rounding), their refusals, what they leave untouched, position independence bit for
-bit, NaN / inf propagation, the host routing in multimodal_gar_amd/bn_ops.py, nn_utils.py and the FP module with a call
+bit, NaN / inf propagation, the I3D entry points of the same kernel (mgar_conv1x1_bf16_fwd[_affine]) as the same contract bit
+for bit on their own timer row, the host routing in multimodal_gar_amd/bn_ops.py, nn_utils.py and the FP module with a call
 census, graph capture, and the drift of bf16 shared MLPs against their fp32 run (train mode) and the float64 chain (eval mode).
 
 Measured on an MI355X: largest err / bound over the 81 unpooled case x prologue x store combinations 0.993 (the bound is the
@@ -116,6 +117,63 @@ def test_pooled_kernel_against_float64_on_the_rounded_operands(pc):
     print("%s: err / bound %.3g" % (what, used))
     assert used <= 1.0, what
     assert torch.equal(bits(y), bits(run_pooled(pc)))
+
+
+# ---- one contract with the I3D entry points -------------------------------------------------------------------------------------
+def _conv1x1(x, w, cout, scale=None, shift=None, relu=0, y=None, ybs=None):
+    """mgar_conv1x1_bf16_fwd, or with a scale mgar_conv1x1_bf16_fwd_affine, called by name -> (rc, y)"""
+    L = _L()
+    n, cin, p = x.shape
+    if y is None:
+        y = torch.full((n, cout, p), CANARY, dtype=BF, device="cuda")
+    ybs = cout * p if ybs is None else ybs
+    if scale is None:
+        rc = L._fns["mgar_conv1x1_bf16_fwd"](L.pptr(x, BF), n, cin, p, L.fptr(w), cout, y.data_ptr(), ybs, L.stream_of(x))
+    else:
+        rc = L._fns["mgar_conv1x1_bf16_fwd_affine"](L.pptr(x, BF), n, cin, p, L.fptr(w), cout, L.fptr(scale), L.fptr(shift), int(relu),
+                                                    y.data_ptr(), ybs, L.stream_of(x))
+    return rc, y
+
+
+@pytest.mark.parametrize("cin,cout,gap", [(20, 24, 0), (40, 40, 0), (72, 96, 64), (136, 160, 0), (520, 264, 0)],
+                         ids=lambda v: str(v))
+def test_conv1x1_entries_and_the_wide_entry_are_one_contract(cin, cout, gap):
+    """The same x, w and scale / shift through mgar_conv1x1_bf16_fwd[_affine] and through mgar_pointwise_wide_bf16_fwd with the
+    identity prologue and w_ld = Cin: identical bits, each call on its own timer row.  One case per Cout tier, ragged channels,
+    P = 132 = a full tile and a 4-column tail; (520, 264) has W in several chunks and 8 waves; ``gap``: y_batch_stride beyond
+    Cout * P, the padding untouched."""
+    L = _L()
+    n, p = 2, 132
+    g = torch.Generator().manual_seed(1000 * cin + cout)
+    x = torch.randn((n, cin, p), generator=g).to(BF).cuda()
+    w = (torch.randn((cout, cin), generator=g) / cin ** 0.5).cuda()
+    scale = (torch.rand((cout,), generator=g) * 2.0 - 0.5).cuda()                       # both signs
+    shift = torch.randn((cout,), generator=g).cuda()
+    ybs = cout * p + gap
+
+    def timed(fn):
+        """-> (y (n, ybs) with its padding, the timer rows the call added to)"""
+        y = torch.full((n, ybs), CANARY, dtype=BF, device="cuda")
+        L.kernel_timers()                                                               # reset
+        rc, _ = fn(y)
+        assert rc == MGAR_OK
+        rows = L.kernel_timers()
+        assert bool((y[:, cout * p:] == CANARY).all())
+        return y, rows
+
+    was_on = L._KT_STATE["on"]
+    L.kernel_timers(enable=True)
+    try:
+        for sc, sh, relu in ((None, None, 0), (scale, shift, 0), (scale, shift, 1)):
+            y1, rows1 = timed(lambda y: _conv1x1(x, w, cout, sc, sh, relu, y=y, ybs=ybs))
+            y2, rows2 = timed(lambda y: launch(x, w, 0, cin, cout, None, sc, sh, relu, y=y, ybs=ybs))
+            assert torch.equal(bits(y1), bits(y2)), (sc is not None, relu)
+            assert not bool((y1[:, :cout * p] == CANARY).all())
+            assert set(rows1) == {"conv1x1_bf16_kernel"} and set(rows2) == {"pointwise_wide_bf16_kernel"}, (rows1, rows2)
+            work = (1, 2.0 * n * p * (cin + cout), 2.0 * n * p * cin * cout)            # launches, bytes, flop
+            assert rows1["conv1x1_bf16_kernel"][1:] == work and rows2["pointwise_wide_bf16_kernel"][1:] == work
+    finally:
+        L.kernel_timers(enable=was_on)
 
 
 def test_refusals_write_nothing():

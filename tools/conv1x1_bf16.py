@@ -3,7 +3,7 @@
     python tools/conv1x1_bf16.py --entry new|affine|mm [--trunk N,P2b,P3,P4 | --shape N,Cin,Cout,P ...] [--warmup 5] [--iters 20]
                                  [--json FILE]
 
-`new` is one launch of mgar_conv1x1_bf16_fwd (csrc/conv1x1_bf16.hip) for all samples, `affine` one launch of
+`new` is one launch of mgar_conv1x1_bf16_fwd (csrc/pointwise_wide_bf16.hip) for all samples, `affine` one launch of
 mgar_conv1x1_bf16_fwd_affine (BatchNorm + ReLU in the store), `mm` the per-sample torch.mm loop of Unit3D._conv with
 MGAR_I3D_K1_BF16=0 (bf16 weight, out= into the sample's slice).  --trunk N,P2b,P3,P4 runs the 29 units up to Mixed_4f at N clips
 with P2b columns for Conv3d_2b_1x1, P3 for Mixed_3b / 3c and P4 for Mixed_4b .. 4f (c2: 4,460800,115200,14400); equal shapes are
