@@ -724,6 +724,30 @@ int mgar_dafm_attn_add_bwd(int S, int total_rows, int D, const int *scene_off, c
                            const float *k, const float *v, float scale, const float *att, const float *grad_out,
                            float *gmat, float *grad_q, float *grad_k, float *grad_v, void *stream);
 
+/* Per-scene MULTI-HEAD attention core over packed scene rows (csrc/scene_mha.hip): what nn.MultiheadAttention(512, 8)
+ * computes between its in- and out-projection when the reference calls it on one scene's rows (cross_attention_fusion,
+ * model/gat_model.py:30-38; FUSION 'catandAtt', :1426-1428).  For every scene s and head h < H, with Q / K / V the head's
+ * 64 columns of the scene's rows:
+ *   Att = softmax(Q K^T * scale, dim=1),   out = Att V
+ * q, k, v: three pointers into fp32 rows of leading dimension ld floats, head h being columns [64 h, 64 h + 64) from each
+ * (the three slices of one fused (rows, 3 * 64 * H) in-projection are passed without a copy); 16-byte aligned, ld % 4 == 0,
+ * ld >= 64 * H.  out: (total_rows, 64 * H) contiguous.  att: (H, pairs), head h's plane packed like de of
+ * mgar_dafm_attn_fwd (block of scene s at h * pairs + de_off[s]); pairs = sum_s n_s^2 from the host.  It is written for the
+ * backward.  scene_off / de_off and the capacity n_s <= MGAR_DAFM_MAX_N (enforced by the caller) as for mgar_dafm_attn_fwd;
+ * empty scenes are allowed.
+ * Checks, all before any device call: a negative size or H, head_dim, ld <= 0 returns MGAR_EINVAL; head_dim != 64,
+ * ld % 4 != 0 or ld < 64 * H returns MGAR_EUNSUPPORTED; then S == 0 or total_rows == 0 returns MGAR_OK with nothing
+ * launched; then a null or misaligned pointer returns MGAR_EINVAL. */
+int mgar_scene_mha_fwd(int S, int total_rows, int H, int head_dim, const int *scene_off, const int *de_off, int pairs,
+                       const float *q, const float *k, const float *v, int ld, float scale, float *att, float *out,
+                       void *stream);
+/* bwd, two passes as mgar_dafm_attn_bwd: rows (dAtt, softmax backward, G = dS * scale into gmat, dq), then columns (dk,
+ * dv).  gmat: (H, pairs) caller-allocated scratch; grad_out and the three gradients: (total_rows, 64 * H) contiguous, the
+ * gradients fully written.  No atomics: every sum has a fixed order and two runs give the same bits. */
+int mgar_scene_mha_bwd(int S, int total_rows, int H, int head_dim, const int *scene_off, const int *de_off, int pairs,
+                       const float *q, const float *k, const float *v, int ld, float scale, const float *att,
+                       const float *grad_out, float *gmat, float *grad_q, float *grad_k, float *grad_v, void *stream);
+
 /* ===================== per-scene operations on PACKED scene rows (scenes of unequal actor counts) =====================
  * The rows of all S scenes are stacked; scene s owns rows [scene_off[s], scene_off[s+1]) and the dense (n_s, n_s) block at
  * de_off[s], exactly as for mgar_dafm_attn_*.  scene_off (S+1) and de_off (S) are int32 DEVICE arrays; total_rows =

@@ -34,7 +34,8 @@ from .backbone import InceptionI3d, NLBlockND
 from .. import vision_ops as TO
 from .. import graph_ops as pyg_nn
 from ..metric_ops import pairwise_cosine_similarity, pairwise_euclidean_distance
-from ..dafm_ops import dafm_attention, dafm_attention_add, scene_offsets
+from ..dafm_ops import dafm_attention, dafm_attention_add, packed_pairs, scene_offsets
+from ..scene_mha_ops import scene_multihead_attention
 from ..scene_ops import scene_batch_norm, scene_gram, scene_layout, scene_pair_geometry
 from ..pcdet.models import build_network, load_data_to_gpu
 
@@ -64,6 +65,18 @@ class cross_attention_fusion(nn.Module):
         L = self.LN_l_1(self.Att1(R, L, L)[0] + L)
         L = self.LN_l_2(self.FFN_r(L) + L)
         return torch.max(torch.stack((R, L)), dim=0)[0]
+
+    def forward_stacked(self, R, L, scene_off, de_off, pairs):
+        """`forward` for the rows of all scenes at once: R, L (sum_s n_s, 512); pairs = sum_s n_s^2 (host int).  The
+        reference's conventions are kept: Att1 and FFN_r serve both branches, the L branch queries with the UPDATED R, and
+        Att2 / FFN_l are never evaluated (no gradient).  The attention core is the HIP kernel of csrc/scene_mha.hip."""
+        def att(query, memory):
+            return scene_multihead_attention(self.Att1, query, memory, memory, scene_off, de_off, pairs)
+        R = self.LN_r_1(att(L, R) + R)
+        R = self.LN_r_2(self.FFN_r(R) + R)
+        L = self.LN_l_1(att(R, L) + L)
+        L = self.LN_l_2(self.FFN_r(L) + L)
+        return torch.max(R, L)
 
 
 class SpaTemp_self_att(nn.Module):
@@ -415,8 +428,31 @@ class Actionhead(nn.Module):
         return tuple(getattr(self, name)(x) for name, _, _ in _HEAD_SPECS)
 
 
-# FUSION values whose scenes can be evaluated together on packed rows (forward_packed); the rest goes scene by scene
-_PACKED_FUSIONS = ('Attention_mat', 'sum', 'Attention_normal', 'Attention_max', 'Attention_multi', 'Attention_gaussian')
+# FUSION values whose scenes can be evaluated together on packed rows (forward_packed); the rest goes scene by scene.
+# MODALITY 'RGB' / 'LiDAR' (one backbone, no fusion) ignore FUSION when fusing but NOT in the adjacency, which the reference
+# keys on FUSION alone: they take the packed route unless FUSION is one of _BILINEAR_ADJACENCY.
+_PACKED_FUSIONS = ('Attention_mat', 'sum', 'Attention_normal', 'Attention_max', 'Attention_multi', 'Attention_gaussian',
+                   'crossAtt', 'catandAtt')
+_BILINEAR_ADJACENCY = ('Attention', 'Attention_sum')     # A_theta = sigmoid(phi sigma^T + sigma phi^T): no packed form
+_PRESENT = {'Multi': (True, True), 'RGB': (True, False), 'LiDAR': (False, True)}   # MODALITY -> (RGB rows, LiDAR rows) used
+
+_PAIR_LOCAL_CACHE = {}
+
+
+def _pair_local(counts, n_max, device):
+    """(pairs,) int64: (s * n_max + i) * n_max + j of every packed pair (s, i, j), its place in a (S, n_max, n_max) tensor
+    viewed flat.  Built on the host once per count tuple and cached, like scene_layout."""
+    key = (tuple(counts), int(n_max), str(device))
+    hit = _PAIR_LOCAL_CACHE.get(key)
+    if hit is None:
+        parts = []
+        for s, n in enumerate(counts):
+            i = torch.arange(n, dtype=torch.int64)
+            parts.append((((s * n_max + i) * n_max)[:, None] + i[None, :]).reshape(-1))
+        hit = (torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64)).to(device)
+        if len(_PAIR_LOCAL_CACHE) < 64:
+            _PAIR_LOCAL_CACHE[key] = hit
+    return hit
 
 
 class GAR_Fusion_Net3(nn.Module):
@@ -595,7 +631,7 @@ class GAR_Fusion_Net3(nn.Module):
         counts = self._scene_counts(RGB_feature, LiDAR_feature, person_id)
         if counts is None:
             return self.forward_per_scene(RGB_feature, LiDAR_feature, bboxes, bboxes3d, social_group_id, person_id)
-        if self.cfg.FUSION == 'Attention_mat' and all(c == counts[0] for c in counts):
+        if self.cfg.MODALITY == 'Multi' and self.cfg.FUSION == 'Attention_mat' and all(c == counts[0] for c in counts):
             return self._forward_batched(RGB_feature, LiDAR_feature, bboxes, bboxes3d, person_id, counts[0])
         return self._forward_ragged(RGB_feature, LiDAR_feature, bboxes, bboxes3d, counts)
 
@@ -655,7 +691,9 @@ class GAR_Fusion_Net3(nn.Module):
         read: `uniform_actor_count` (one int for every scene) or `actor_counts` (a sequence of host ints, one per scene); where
         both are set, `uniform_actor_count` is the one that holds.  A promised count is taken as given: a caller that promises
         as many actors as there are slots gets them all, where the derived count of such a scene is one short (below)."""
-        if RGB_feature is None or LiDAR_feature is None or not self._scene_counts_ok([2]):
+        use_r, use_l = _PRESENT.get(self.cfg.MODALITY, (True, True))
+        present = [t for t, used in ((RGB_feature, use_r), (LiDAR_feature, use_l)) if used]    # a single modality: the other
+        if any(t is None for t in present) or not self._scene_counts_ok([2]):                  # tensor may be None
             return None
         S, MNP = person_id.shape
         if S == 0:
@@ -680,15 +718,18 @@ class GAR_Fusion_Net3(nn.Module):
             if not host[-1]:
                 return None
             counts = host[:-1]
-        if not self._scene_counts_ok(counts) or min(RGB_feature.shape[1], LiDAR_feature.shape[1]) < max(counts):
+        if not self._scene_counts_ok(counts) or min(t.shape[1] for t in present) < max(counts):
             return None
         return counts
 
     def _scene_counts_ok(self, counts):
         """Whether scenes of these actor counts can take a batched route under this configuration."""
         cfg = self.cfg
-        ok = (cfg.MODALITY == 'Multi' and cfg.FUSION in _PACKED_FUSIONS and cfg.sim == 'cosine' and cfg.FEAT_NORM
-              and cfg.get("ind_action_concat") and not cfg.get("sg_feat_org") and not cfg.get("Social_Layer")
+        # Multi: the fusions with a packed form, under FEAT_NORM; one modality: with FEAT_NORM or without it, under every
+        # FUSION whose adjacency _adjacency_packed mirrors
+        ok = (((cfg.MODALITY == 'Multi' and cfg.FUSION in _PACKED_FUSIONS and cfg.FEAT_NORM)
+               or (cfg.MODALITY in ('RGB', 'LiDAR') and cfg.FUSION not in _BILINEAR_ADJACENCY))
+              and cfg.sim == 'cosine' and cfg.get("ind_action_concat") and not cfg.get("sg_feat_org") and not cfg.get("Social_Layer")
               and not cfg.get("Social_Encoder") and not cfg.get("Action_concat") and not cfg.get("DISABLE_BATCHED"))
         return bool(ok) and len(counts) > 0 and min(counts) >= 2 and max(counts) <= 128
 
@@ -754,12 +795,13 @@ class GAR_Fusion_Net3(nn.Module):
     def _forward_ragged(self, RGB_feature, LiDAR_feature, bboxes, bboxes3d, counts):
         """The batched route for scenes of unequal actor counts: the valid rows of the padded inputs, packed."""
         S, MNP = bboxes.shape[0], bboxes.shape[1]
-        device = RGB_feature.device
+        device = bboxes.device
+        use_r, use_l = _PRESENT.get(self.cfg.MODALITY, (True, True))
 
         def rows_of(t):                                 # the padded width is each tensor's own
             return t.reshape(S * t.shape[1], t.shape[2])[scene_layout(counts, t.shape[1], device).row_slot]
-        return self.forward_packed(rows_of(RGB_feature), rows_of(LiDAR_feature), rows_of(bboxes), rows_of(bboxes3d)[:, :3],
-                                   counts, MNP)
+        return self.forward_packed(rows_of(RGB_feature) if use_r else None, rows_of(LiDAR_feature) if use_l else None,
+                                   rows_of(bboxes), rows_of(bboxes3d)[:, :3], counts, MNP)
 
     def _packed_bn(self, bn, x, scene_off):
         if not self.training:
@@ -769,8 +811,19 @@ class GAR_Fusion_Net3(nn.Module):
 
     def _fuse_packed(self, R, L, de, dg, so, do, pairs=None):
         """`_fuse` for the packed rows of all scenes (the configurations of _PACKED_FUSIONS): de, dg are the scenes' flat
-        (n_s, n_s) matrices, so / do their offsets, pairs = sum n_s^2 (host int; None: read back from the device)."""
+        (n_s, n_s) matrices, so / do their offsets, pairs = sum n_s^2 (host int; None: read back from the device).  Under
+        MODALITY 'RGB' / 'LiDAR' the absent side is None and the present rows are the result."""
         fus = self.cfg.FUSION
+        if self.cfg.MODALITY == 'RGB':
+            return R
+        if self.cfg.MODALITY == 'LiDAR':
+            return L
+        if fus == 'crossAtt':
+            return self.AttFusModule.forward_stacked(R, L, so, do, packed_pairs(so) if pairs is None else pairs)
+        if fus == 'catandAtt':
+            x = self.FL(torch.cat([R, L], dim=1))
+            x = self.LN(x + scene_multihead_attention(self.Att, x, x, x, so, do, packed_pairs(so) if pairs is None else pairs))
+            return self.LN2(self.FL2(x) + x)
         if fus == 'Attention_mat':
             Rp, Lp = self.AttFusModule1.forward_stacked(R, L, de, so, do)
             Rp, Lp = self.AttFusModule2.forward_stacked(Rp, Lp, de, so, do)
@@ -793,20 +846,45 @@ class GAR_Fusion_Net3(nn.Module):
             return torch.max(Rp, Lp)
         raise NotImplementedError("GAR_MODEL.FUSION = %r has no packed route" % fus)
 
+    def _adjacency_packed(self, fused, de, dg, lay):
+        """`_adjacency` for the packed pairs of all scenes -> (sum n_s^2,).  Like `_adjacency` it is keyed on FUSION alone,
+        whatever MODALITY is; the bilinear form of _BILINEAR_ADJACENCY has no packed mirror and raises."""
+        if self.cfg.FUSION in _BILINEAR_ADJACENCY:
+            raise NotImplementedError("GAR_MODEL.FUSION = %r: its adjacency has no packed route" % self.cfg.FUSION)
+        if self.cfg.FUSION == 'crossAtt':
+            # reference :1532-1544: [a_i - a_j, Dg_ij, De_ij] through the 32 -> 8 -> 1 D_embed; Dv is not read, so no Gram
+            # matrix.  The differences are formed on a (S, n_max, n_max) grid and the packed pairs gathered from it: every
+            # index below hits each of its targets once, so the backward sums in a fixed order (plain torch: n^2 * 32 work).
+            # Gathering a[i] - a[j] straight from the rows would scatter-add n gradients into every row in the backward, in
+            # no fixed order.  The price is the grid: S * n_max^2 * 30 floats, in the forward and again in the backward --
+            # 15 MB at 120 scenes of 32 actors, 236 MB if ONE of 120 scenes holds 128 (DESIGN.md section 3.8).
+            S, n_max = len(lay.counts), lay.n_max
+            a = self.F_embed(fused)
+            a = a.new_zeros(S * n_max, a.shape[1]).index_copy(0, lay.row_local, a).view(S, n_max, -1)
+            diff = (a[:, :, None, :] - a[:, None, :, :]).reshape(S * n_max * n_max, -1)
+            diff = diff.index_select(0, _pair_local(lay.counts, n_max, fused.device))
+            return self.D_embed(torch.cat((diff, dg[:, None], de[:, None]), dim=1)).reshape(-1)
+        fn = fused / fused.norm(dim=1, keepdim=True)
+        Dv = scene_gram(fn, lay.scene_off, lay.de_off, lay.pairs)
+        return self.D_embed(torch.stack((Dv, dg), dim=-1)).reshape(-1)
+
     def forward_packed(self, R, L, bb, ctr, counts, MNP):
         """R, L (rows, 512), bb (rows, 4) xyxy, ctr (rows, 3): the rows of all scenes stacked, scene s holding counts[s] of
         them (host ints, each 2..MGAR_DAFM_MAX_N) -> the 16 zero-padded (S, MNP, .) tensors of forward().  Every step is one
-        launch sequence for all scenes; with a count tuple seen before, nothing reads from or writes to the host."""
-        S, device = len(counts), R.device
+        launch sequence for all scenes; with a count tuple seen before, nothing reads from or writes to the host.  Under
+        MODALITY 'RGB' / 'LiDAR' the absent one of R, L is None (and ignored if given)."""
+        cfg = self.cfg
+        use_r, use_l = _PRESENT.get(cfg.MODALITY, (True, True))
+        R, L = (R if use_r else None), (L if use_l else None)
+        S, device = len(counts), bb.device
         lay = scene_layout(counts, MNP, device)
         so, do = lay.scene_off, lay.de_off
-        R = self._packed_bn(self.bn_rgb, R, so)
-        L = self._packed_bn(self.bn_lidar, L, so)
+        if cfg.FEAT_NORM:                               # BatchNorm on what is present, as forward_per_scene
+            R = None if R is None else self._packed_bn(self.bn_rgb, R, so)
+            L = None if L is None else self._packed_bn(self.bn_lidar, L, so)
         de, dg = scene_pair_geometry(ctr, bb, so, do, lay.pairs)
         fused = self._fuse_packed(R, L, de, dg, so, do, lay.pairs)
-        fn = fused / fused.norm(dim=1, keepdim=True)
-        Dv = scene_gram(fn, so, do, lay.pairs)
-        A_theta = self.D_embed(torch.stack((Dv, dg), dim=-1)).reshape(-1)                        # (sum n_s^2,)
+        A_theta = self._adjacency_packed(fused, de, dg, lay)                                     # (sum n_s^2,)
         if not self.training:
             A_theta = A_theta.index_fill(0, lay.diag_index, 1.)
         A_list = torch.zeros(S * MNP * MNP, device=device, dtype=A_theta.dtype).index_put((lay.pair_index,), A_theta)
@@ -817,7 +895,7 @@ class GAR_Fusion_Net3(nn.Module):
         group_id = torch.where(tmp >= 0.5, cols, torch.full_like(cols, MNP)).min(dim=2).values  # (S, MNP)
         gflat = group_id.reshape(-1)[lay.row_slot] + so.long()[lay.row_scene]
         sg_features = self._group_max_pool(fused, gflat)
-        res_feature = torch.cat([R, L], dim=-1)
+        res_feature = torch.cat([R, L], dim=-1) if use_r and use_l else (R if use_r else L)
         outs = []
         for prefix, feat in (("", res_feature), ("SG_", sg_features)):
             outs += self._heads_stacked(prefix, feat, S, None, MNP, lay.row_slot)

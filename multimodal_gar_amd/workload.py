@@ -67,12 +67,22 @@ def lidar_model_cfg(n_points, route="pointnet2"):
     raise ValueError(route)
 
 
-def model_cfg(n_actors, n_points, gat=True, route="pointnet2", fusion="Attention_mat"):
+def model_cfg(n_actors, n_points, gat=True, route="pointnet2", fusion="Attention_mat", modality="Multi"):
     """The shipped configuration (Multimodal_cfg/mil3.yaml) with the synthetic sizes plugged in.  fusion: GAR_MODEL.FUSION, the
     shipped DAFM by default; the ablation variants with fixed sigmas (Attention_multi, Attention_gaussian) take them from
-    their classes, SIGMA is for the others.
+    their classes, SIGMA is for the others.  modality: "Multi", or "RGB" / "LiDAR" for the single-modality baselines, which
+    run without feature normalisation (the reference raises on them with FEAT_NORM) and with 512-wide individual heads.
     GAT_module is False in the shipped YAML (:86); the north-star includes the GAT path, so the
     benchmark flips it on (SURVEY.md "facts")."""
+    if modality not in ("Multi", "RGB", "LiDAR"):
+        raise ValueError("modality: 'Multi', 'RGB' or 'LiDAR', got %r" % (modality,))
+    cfg = _model_cfg(n_actors, n_points, gat, route, fusion)
+    if modality != "Multi":
+        cfg.GAR_MODEL.update(MODALITY=modality, FEAT_NORM=False, FEATURE_DIM=512)
+    return cfg
+
+
+def _model_cfg(n_actors, n_points, gat, route, fusion):
     return EasyDict(
         DATALOADER=dict(train=dict(augmentation=dict(num_boxes=n_actors + 1, image_size=[720, 1280], crop_size=5))),
         RGB_BACKBONE=dict(I3D_FREEZE=True, EMBEDDING_DIM=512, INTER_PERSON=False, GAT_module=bool(gat), two_stage_att=False),
@@ -138,10 +148,11 @@ def make_batch(seed, n_clips, n_frames, n_actors, n_points, height, width, devic
 class ClipModel(nn.Module):
     """GAR_Fusion_ALL plus the clip/frame plumbing described in the module docstring."""
 
-    def __init__(self, n_actors, n_points, gat=True, route="pointnet2", fusion="Attention_mat"):
+    def __init__(self, n_actors, n_points, gat=True, route="pointnet2", fusion="Attention_mat", modality="Multi"):
         super().__init__()
         from .model.gat_model import GAR_Fusion_ALL
-        self.cfg = model_cfg(n_actors, n_points, gat, route, fusion)
+        self.cfg = model_cfg(n_actors, n_points, gat, route, fusion, modality)
+        self.modality = modality        # "RGB" / "LiDAR": GAR_Fusion_ALL builds that backbone alone
         self.route = route
         self.n_actors = n_actors
         self.dataset = SyntheticDataset()
@@ -279,7 +290,9 @@ class ClipModel(nn.Module):
         return counts
 
     def forward(self, batch):
-        """Picks one of three stream schedules; each joins its side streams into the issuing stream before the fusion net."""
+        """Picks one of the stream schedules; each joins its side streams into the issuing stream before the fusion net."""
+        if self.modality != "Multi":
+            return self._forward_single(batch)
         if not (batch["images"].is_cuda and self.overlap_branches):
             return self._forward_serial(batch)
         if (self.geometry_prefetch and self.route == "pointnet2") or self.rgb_prefetch:
@@ -291,6 +304,16 @@ class ClipModel(nn.Module):
         counts = self._counts(batch)
         rgb = self.rgb_tokens(batch["images"], batch["bboxes"], counts)            # (B, A, 512)
         lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"], None, counts)   # (B*T, A, 512)
+        return self._fuse(batch, rgb, lidar, counts)
+
+    def _forward_single(self, batch):
+        """One modality: its branch and the fusion net on the current stream, no fork; the absent side is None."""
+        counts = self._counts(batch)
+        rgb = lidar = None
+        if self.modality == "RGB":
+            rgb = self.rgb_tokens(batch["images"], batch["bboxes"], counts)
+        else:
+            lidar = self.lidar_tokens(batch["points"], batch["bboxes3d"], None, counts)
         return self._fuse(batch, rgb, lidar, counts)
 
     def _forward_forked(self, batch):
@@ -388,13 +411,15 @@ class ClipModel(nn.Module):
         if counts is not None:
             return self._fuse_ragged(batch, rgb, lidar, counts)
         b, t, a = batch["n_clips"], batch["n_frames"], self.n_actors
-        rgb_s = rgb[:, None].expand(b, t, a, rgb.shape[-1]).reshape(b * t, a, -1)   # every frame-scene of a clip
-        pad = lambda x: torch.cat([x, x.new_zeros(x.shape[0], 1, x.shape[2])], 1)    # noqa: E731  -> MNP = A + 1
+        if rgb is not None:
+            rgb = rgb[:, None].expand(b, t, a, rgb.shape[-1]).reshape(b * t, a, -1)  # every frame-scene of a clip
+        # MNP = A + 1; a single-modality model passes None for the absent side
+        pad = lambda x: None if x is None else torch.cat([x, x.new_zeros(x.shape[0], 1, x.shape[2])], 1).float()  # noqa: E731
         bb2 = batch["bboxes"][:, None].expand(b, t, a + 1, 4).reshape(b * t, a + 1, 4)
         # The fusion net works on (A, 512) tokens per scene: launch-bound, not bandwidth-bound.  It runs in fp32 on every
         # configuration (under the bf16 configurations the token producers above are bf16; the tokens are widened here).
-        with torch.autocast(device_type=rgb_s.device.type, enabled=False):
-            return self.net.GAR_model(pad(rgb_s.float()), pad(lidar.float()), bb2, batch["bboxes3d"], None, batch["person_id"])
+        with torch.autocast(device_type=bb2.device.type, enabled=False):
+            return self.net.GAR_model(pad(rgb), pad(lidar), bb2, batch["bboxes3d"], None, batch["person_id"])
 
     def _fuse_ragged(self, batch, rgb, lidar, counts):
         """rgb: the clips' tokens packed (sum of the clips' counts, 512); lidar: the frame-scenes' tokens packed.  Every
@@ -403,19 +428,20 @@ class ClipModel(nn.Module):
         from .scene_ops import scene_layout
         t, mnp = batch["n_frames"], self.n_actors + 1
         frames = _frame_counts(counts, t)
-        dev = lidar.device
+        dev = batch["bboxes"].device
         tok_rows, box_rows = _clip_rows(counts, t, mnp, dev)
         slot = scene_layout(frames, mnp, dev).row_slot
         gar = self.net.GAR_model
         with torch.autocast(device_type=dev.type, enabled=False):
-            R, L = rgb.float()[tok_rows], lidar.float()
+            R = None if rgb is None else rgb.float()[tok_rows]           # a single-modality model: the absent side is None
+            L = None if lidar is None else lidar.float()
             bb = batch["bboxes"].reshape(-1, 4)[box_rows]
             b3 = batch["bboxes3d"].reshape(-1, batch["bboxes3d"].shape[-1])[slot]
             if gar._scene_counts_ok(frames):
                 return gar.forward_packed(R, L, bb, b3[:, :3], frames, mnp)
             # scene by scene, as the reference loops: the same rows in the zero-padded tensors of its interface
             s = len(frames)
-            pad = lambda x: x.new_zeros(s * mnp, x.shape[1]).index_copy(0, slot, x).view(s, mnp, -1)    # noqa: E731
+            pad = lambda x: None if x is None else x.new_zeros(s * mnp, x.shape[1]).index_copy(0, slot, x).view(s, mnp, -1)  # noqa: E731
             return gar.forward_per_scene(pad(R), pad(L), pad(bb), batch["bboxes3d"], None, batch["person_id"])
 
 
@@ -558,11 +584,11 @@ class TrainStep(_GraphStep):
     (no DDP wrapper: its hooks cannot live inside a captured backward), then Adam."""
 
     def __init__(self, n_actors, n_points, device, gat=True, route="pointnet2", ddp=False, lr=1e-3, seed=2023,
-                 manual_allreduce=False, loss="reference", fusion="Attention_mat"):
+                 manual_allreduce=False, loss="reference", fusion="Attention_mat", modality="Multi"):
         assert loss in ("reference", "synthetic")
         self.loss_kind = loss
         torch.manual_seed(seed)  # the reference seeds 2023 (train_func.py:45-47)
-        self.model = ClipModel(n_actors, n_points, gat, route, fusion).to(device)
+        self.model = ClipModel(n_actors, n_points, gat, route, fusion, modality).to(device)
         self.model.train()
         self.module = self.model
         self.manual_allreduce = bool(manual_allreduce)
@@ -679,15 +705,15 @@ class ForwardStep(_GraphStep):
     the fp32 run.  Same interface as TrainStep (capture / run / run_eager, .module, .graph)."""
 
     def __init__(self, n_actors, n_points, device, gat=True, route="pointnet2", precision="fp32", seed=2023,
-                 fusion="Attention_mat"):
+                 fusion="Attention_mat", modality="Multi"):
         assert precision in ("fp32", "bf16")
         torch.manual_seed(seed)
-        self.model = ClipModel(n_actors, n_points, gat, route, fusion).to(device)
+        self.model = ClipModel(n_actors, n_points, gat, route, fusion, modality).to(device)
         self.model.train()
         self.module = self.model
         self.precision = precision
         self.device = device
-        if precision == "bf16":
+        if precision == "bf16" and modality != "LiDAR":
             # the frozen I3D's convolution weights are converted once (autocast would re-cast them every step);
             # BatchNorm vectors and every trainable parameter stay fp32
             for m in self.model.net.RGB_backbone.backbone_net.modules():
