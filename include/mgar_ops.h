@@ -868,6 +868,30 @@ int mgar_voxel_roi_pool_eval_fwd(int M, int nsample, int C, int Co, const float 
                                  const float *pos_shift, const float *w_out, const float *out_scale, const float *out_shift,
                                  int relu, float *out, int ld_out, void *stream);
 
+/* ============ non-local block, inference (model/backbone.py NLBlockND, mode 'dot', every BatchNorm on running statistics) ====
+ * One launch, no workspace, no atomics.  Per sample a < n, with x_a the (C, P) matrix whose element (c, p) lies at
+ * x + a*sx_n + c*sx_c + p*sx_p (strides in elements; (n, C, P) contiguous is sx = (C*P, P, 1), rows (n, P, C) is (P*C, 1, C)):
+ *   [T; Phi; G] = w_tpg x_a + b_tpg      w_tpg (3 Ci, C): theta, phi, g stacked; (Ci, P) each
+ *   S = G Phi^T / P                      (Ci, Ci): 'dot' mode has no softmax, so y = (theta^T phi / P) g = theta^T ((phi g^T) / P)
+ *   Y = S T                              (Ci, P)     and the (P, P) matrix is never formed
+ *   z[a] = fmaf(w_z Y + b_z, scale, shift) + x_a          w_z (C, Ci); z (n, C, P) contiguous
+ * scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale for a block with a BatchNorm behind W_z, 1 and 0
+ * without one.  fp32 arithmetic: every product an exact-fp32 MFMA (a k-ordered fmaf chain) whose k order depends on
+ * (C, Ci, P) alone; T, Phi, G, S, Y stay in LDS; x is streamed once and read a second time, by the workgroup that streamed it,
+ * for the residual.  A sample's bits depend on that sample and the parameters only -- not on n, its position or its workgroup
+ * neighbours; a NaN stays inside its sample.  Parameters fp32 and required.  Supported (mgar_nonlocal_dot_eval_supported
+ * returns 1, else 0): 1 <= C <= 1024, 1 <= Ci <= 128, 1 <= P <= 256, Ci * P <= 4096; outside it MGAR_EUNSUPPORTED.  n < 0, a size
+ * < 1, a negative stride or a null pointer with n > 0 is MGAR_EINVAL; n == 0 returns MGAR_OK with nothing launched; every refusal
+ * precedes any device call.  Forward only.  mgar_nonlocal_dot_eval_bf16_fwd reads bf16 x and rounds z once, to nearest even; it
+ * is called by name, not as a `_bf16` payload twin of the table at the end of this header. */
+int mgar_nonlocal_dot_eval_supported(int C, int Ci, int P);
+int mgar_nonlocal_dot_eval_fwd(const float *x, long long sx_n, long long sx_c, long long sx_p, int n, int C, int Ci, int P,
+                               const float *w_tpg, const float *b_tpg, const float *w_z, const float *b_z, const float *scale,
+                               const float *shift, float *z, void *stream);
+int mgar_nonlocal_dot_eval_bf16_fwd(const void *x, long long sx_n, long long sx_c, long long sx_p, int n, int C, int Ci, int P,
+                                    const float *w_tpg, const float *b_tpg, const float *w_z, const float *b_z, const float *scale,
+                                    const float *shift, void *z, void *stream);
+
 /* ============ sparse 3-D convolution: trunk of Voxel R-CNN ====================
  * Replaces the third-party spconv calls of pcdet/models/backbones_3d/spconv_backbone.py:69-170 (SubMConv3d /
  * SparseConv3d) and the dense voxel -> row table of pcdet/utils/common_utils.py:235-252 as a lookup structure.

@@ -29,7 +29,7 @@ const char *const kKtNames[KT_COUNT] = {
     "dafm_attn_fwd", "dafm_attn_bwd", "gatv2_fwd", "gatv2_bwd", "roi_align_fwd", "roi_align_bwd", "voxel_query_kernel", "points_in_boxes_kernel",
     "roipoint_pool3d_kernel", "spconv_index", "spconv_gemm", "spconv_dw", "point_grid_build", "ball_query_grid_kernel", "three_nn_grid_kernel", "conv3d_wino_kernel", "conv3d_bf16_kernel",
     "spconv_bf16_kernel", "pointwise_bf16_kernel", "conv1x1_bf16_kernel",
-    "pointwise_wide_bf16_kernel", "voxel_roi_pool_eval"};
+    "pointwise_wide_bf16_kernel", "nonlocal_dot_eval", "voxel_roi_pool_eval"};
 }  // namespace
 
 void kt_begin(int id, hipStream_t st) {

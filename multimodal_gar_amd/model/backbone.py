@@ -599,7 +599,12 @@ class NLBlockND(nn.Module):
             self.W_f = nn.Sequential(nn.Conv2d(self.inter_channels * 2, 1, kernel_size=1), nn.ReLU())
 
     def forward(self, x):
-        """x: (N, C, T, H, W) / (N, C, H, W) / (N, C, T) for dimension 3 / 2 / 1."""
+        """x: (N, C, T, H, W) / (N, C, H, W) / (N, C, T) for dimension 3 / 2 / 1.  Inference in mode 'dot' (nonlocal_ops.nl_eval_plan)
+        is one launch of csrc/nonlocal_eval.hip; everything else runs the ops below."""
+        from .. import nonlocal_ops
+        plan = nonlocal_ops.nl_eval_plan(self, x)
+        if plan is not None:
+            return nonlocal_ops.nl_eval_forward(self, x, plan)
         n = x.size(0)
         g_x = conv1x1(self.g, x).view(n, self.inter_channels, -1).permute(0, 2, 1)  # (N, P, Ci)
         if self.mode == 'gaussian':
@@ -629,6 +634,16 @@ class NLBlockND(nn.Module):
         y = torch.matmul(f_div_c, g_x).permute(0, 2, 1).contiguous()
         y = y.view(n, self.inter_channels, *x.size()[2:])
         return (self.W_z(y) if isinstance(self.W_z, nn.Sequential) else conv1x1(self.W_z, y)) + x
+
+    def forward_rows(self, rows):
+        """rows: (N, P, C) row-major, the block's input with the positions flattened and the channels last -> (N, C, P).  On the
+        inference route the kernel reads the rows through their strides: the transposing copy in front of ``forward`` is gone."""
+        from .. import nonlocal_ops
+        plan = nonlocal_ops.nl_eval_plan(self, rows, rows=True)
+        if plan is not None:
+            return nonlocal_ops.nl_eval_forward(self, rows, plan, rows=True)
+        n, p, c = rows.shape
+        return self.forward(rows.permute(0, 2, 1).reshape(n, c, p, *([1] * (self.dimension - 1)))).reshape(n, c, p)
 
 
 def _needs_torchvision(name):

@@ -34,6 +34,7 @@ from .backbone import InceptionI3d, NLBlockND
 from .. import vision_ops as TO
 from .. import graph_ops as pyg_nn
 from ..metric_ops import pairwise_cosine_similarity, pairwise_euclidean_distance
+from ..nonlocal_ops import nl_eval_plan
 from ..dafm_ops import dafm_attention, dafm_attention_add, packed_pairs, scene_offsets
 from ..scene_mha_ops import scene_multihead_attention
 from ..scene_ops import scene_batch_norm, scene_gram, scene_layout, scene_pair_geometry
@@ -312,6 +313,11 @@ class LiDAR_Backbone(nn.Module):
         if not lc.SELF_ATT1.USE:
             return self.LiDAR_feature_processing(out)
         assert lc.SELF_ATT1.DIM == 3
+        nl = self.self_attention_net1
+        if not (lc.SELF_ATT1.INTER_PERSON or nl._forward_hooks or nl._forward_pre_hooks) \
+                and nl_eval_plan(nl, out['pooled_features'], rows=True) is not None:
+            grid = nl.forward_rows(out['pooled_features'])   # inference: the (NP, 216, 96) rows as they are (a hook wants __call__)
+            return self.embedding(grid.reshape(1, grid.shape[0], -1))
         grid = self._as_grid(out['pooled_features'])                         # (NP, 96, 6, 6, 6)
         if not lc.SELF_ATT1.INTER_PERSON:
             grid = self.self_attention_net1(grid)

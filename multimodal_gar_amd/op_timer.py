@@ -126,7 +126,7 @@ KERNEL_SOURCES = {
     "roi_align_bwd": "roi_align.hip", "voxel_query_kernel": "voxel_query.hip", "conv3d_wino_kernel": "conv3d_wino.hip",
     "conv3d_bf16_kernel": "conv3d_bf16.hip", "spconv_bf16_kernel": "sparse_conv_bf16.hip", "voxel_roi_pool_eval": "voxel_roi_pool.hip",
     "pointwise_bf16_kernel": "pointwise_bf16.hip", "conv1x1_bf16_kernel": "pointwise_wide_bf16.hip",
-    "pointwise_wide_bf16_kernel": "pointwise_wide_bf16.hip",
+    "pointwise_wide_bf16_kernel": "pointwise_wide_bf16.hip", "nonlocal_dot_eval": "nonlocal_eval.hip",
 }
 
 
