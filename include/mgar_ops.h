@@ -794,6 +794,24 @@ int mgar_scene_gram_fwd(int S, int total_rows, int D, const int *scene_off, cons
 int mgar_scene_gram_bwd(int S, int total_rows, int D, const int *scene_off, const int *de_off, const float *x,
                         const float *grad_g, float *grad_x, void *stream);
 
+/* Eval-mode tail of the fusion net behind the fused rows (GAR_Fusion_Net3.forward_per_scene in eval mode, between _fuse and
+ * the heads), one workgroup per scene, forward only.  fused (total_rows, D) fp32 packed scene rows, D % 64 == 0; dg: the
+ * packed GIoU pairs of mgar_scene_pair_geometry; scene_off / de_off as there.  Per scene of n rows:
+ *   Dv_ij = <x_i, x_j> / (|x_i| |x_j|)   (the dot product and |x_i|^2 each one fused-multiply-add chain over d ascending)
+ *   a_ij  = D_embed([Dv_ij, Dg_ij]), a_ii = 1;  a_list (S, mnp, mnp): the scene's whole block, padding zeros included
+ *   group_id (S, mnp) int32: smallest j with a_ij >= 0.5 (a NaN compares false), -1 in the padding slots
+ *   sg (total_rows, D): row i = max over {k : group_id_k == group_id_i} of x_k, a NaN member giving NaN
+ *   card (S, D + 1): column maxima of the scene's rows (NaN propagating), then the sum of the (n, n) block of a
+ * dembed (device floats): hidden == 0: [w_v, w_g, b] of Linear(2, 1) + Sigmoid; hidden == H <= 8: W1 (H, 2) row-major,
+ * b1 (H), w2 (H), b2 of Linear(2, H) + ReLU + Linear(H, 1) + Sigmoid.  No atomics, no workspace; every sum has an order
+ * that depends on (n, D, hidden) alone, a scene's bits depend on that scene and the parameters only, a NaN stays inside
+ * its scene.  scene_off is a device pointer, so the caller passes the smallest and largest scene size it laid the rows
+ * out from: n_min < 2, n_max > MGAR_DAFM_MAX_N, n_max > mnp, D % 64 != 0 or hidden > 8 return MGAR_EUNSUPPORTED, a
+ * non-positive size, a negative hidden or a null pointer MGAR_EINVAL, all before any device call; S == 0 returns MGAR_OK. */
+int mgar_scene_tail_eval_fwd(int S, int total_rows, int D, int mnp, int n_min, int n_max, const int *scene_off,
+                             const int *de_off, const float *fused, const float *dg, const float *dembed, int hidden,
+                             float *a_list, int *group_id, float *sg, float *card, void *stream);
+
 /* GATv2 edge-softmax + aggregate (torch_geometric.nn.GATv2Conv arithmetic; call site
  * model/gat_model.py:1082-1094).  Edges are given in CSR form grouped by TARGET node:
  * rowptr (n_nodes+1), col (E) = source node of each incoming edge (self loops included

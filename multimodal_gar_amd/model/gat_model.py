@@ -38,6 +38,7 @@ from ..nonlocal_ops import nl_eval_plan
 from ..dafm_ops import dafm_attention, dafm_attention_add, packed_pairs, scene_offsets
 from ..scene_mha_ops import scene_multihead_attention
 from ..scene_ops import scene_batch_norm, scene_gram, scene_layout, scene_pair_geometry
+from .. import scene_tail_ops
 from ..pcdet.models import build_network, load_data_to_gpu
 
 
@@ -743,7 +744,7 @@ class GAR_Fusion_Net3(nn.Module):
         """BatchNorm1d applied to every scene separately (per-scene statistics, like the reference's
         loop), for x (S, N, C).  Running statistics receive the same sequence of EMA updates."""
         if not self.training:
-            return (x - bn.running_mean) / torch.sqrt(bn.running_var + bn.eps) * bn.weight + bn.bias
+            return _eval_bn(bn, x)
         mean = x.mean(dim=1, keepdim=True)
         var = x.var(dim=1, unbiased=False, keepdim=True)
         y = (x - mean) / torch.sqrt(var + bn.eps) * bn.weight + bn.bias
@@ -776,9 +777,20 @@ class GAR_Fusion_Net3(nn.Module):
         Rp, Lp = self.AttFusModule1.forward_stacked(Rf, Lf, de_flat, so, do)
         Rp, Lp = self.AttFusModule2.forward_stacked(Rp, Lp, de_flat, so, do)
         fused = torch.max(Rp, Lp).view(S, n, -1)
+        Dg = torch.stack([TO.generalized_box_iou(bb[s], bb[s]) for s in range(S)]) if S <= 4 else _giou_batched(bb)
+        self._tail_group_id = None
+        if scene_tail_ops.scene_tail_plan(self, fused.view(S * n, -1), [n] * S) is not None:
+            # eval mode: the whole tail behind the fused rows in one launch (scene_tail_ops); Dg stays the tensor above
+            lay = scene_layout([n] * S, MNP, device)
+            A_list, self._tail_group_id, sg_features, card_feature = scene_tail_ops.scene_tail_eval(
+                fused.view(S * n, -1), Dg.reshape(-1), lay, self.D_embed)
+            res_feature = torch.cat([Rf, Lf], dim=-1)
+            outs = []
+            for prefix, feat in (("", res_feature), ("SG_", sg_features)):
+                outs += self._heads_stacked(prefix, feat, S, n, MNP)
+            return (A_list, *outs, self.card_net(card_feature))
         fn = fused / fused.norm(dim=2, keepdim=True)
         Dv = fn @ fn.transpose(1, 2)
-        Dg = torch.stack([TO.generalized_box_iou(bb[s], bb[s]) for s in range(S)]) if S <= 4 else _giou_batched(bb)
         A_theta = self.D_embed(torch.stack((Dv, Dg), dim=-1).reshape(-1, 2)).reshape(S, n, n)
         eye = torch.eye(n, device=device, dtype=torch.bool)
         if not self.training:
@@ -811,7 +823,7 @@ class GAR_Fusion_Net3(nn.Module):
 
     def _packed_bn(self, bn, x, scene_off):
         if not self.training:
-            return (x - bn.running_mean) / torch.sqrt(bn.running_var + bn.eps) * bn.weight + bn.bias
+            return _eval_bn(bn, x)
         return scene_batch_norm(x, bn.weight, bn.bias, scene_off, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                 bn.eps, bn.momentum)
 
@@ -890,6 +902,15 @@ class GAR_Fusion_Net3(nn.Module):
             L = None if L is None else self._packed_bn(self.bn_lidar, L, so)
         de, dg = scene_pair_geometry(ctr, bb, so, do, lay.pairs)
         fused = self._fuse_packed(R, L, de, dg, so, do, lay.pairs)
+        res_feature = torch.cat([R, L], dim=-1) if use_r and use_l else (R if use_r else L)
+        self._tail_group_id = None
+        if scene_tail_ops.scene_tail_plan(self, fused, counts) is not None:
+            # eval mode: the whole tail behind the fused rows in one launch (scene_tail_ops)
+            A_list, self._tail_group_id, sg_features, card_feature = scene_tail_ops.scene_tail_eval(fused, dg, lay, self.D_embed)
+            outs = []
+            for prefix, feat in (("", res_feature), ("SG_", sg_features)):
+                outs += self._heads_stacked(prefix, feat, S, None, MNP, lay.row_slot)
+            return (A_list, *outs, self.card_net(card_feature))
         A_theta = self._adjacency_packed(fused, de, dg, lay)                                     # (sum n_s^2,)
         if not self.training:
             A_theta = A_theta.index_fill(0, lay.diag_index, 1.)
@@ -901,7 +922,6 @@ class GAR_Fusion_Net3(nn.Module):
         group_id = torch.where(tmp >= 0.5, cols, torch.full_like(cols, MNP)).min(dim=2).values  # (S, MNP)
         gflat = group_id.reshape(-1)[lay.row_slot] + so.long()[lay.row_scene]
         sg_features = self._group_max_pool(fused, gflat)
-        res_feature = torch.cat([R, L], dim=-1) if use_r and use_l else (R if use_r else L)
         outs = []
         for prefix, feat in (("", res_feature), ("SG_", sg_features)):
             outs += self._heads_stacked(prefix, feat, S, None, MNP, lay.row_slot)
@@ -931,15 +951,20 @@ class GAR_Fusion_Net3(nn.Module):
             return outs
         ks = [k for _, k, _ in _HEAD_SPECS]
         hid_dim = heads[0][0].out_features
-        w1 = torch.cat([h[0].weight for h in heads], 0)
-        b1 = torch.cat([h[0].bias for h in heads], 0)
-        hid = F.dropout(F.relu(F.linear(feat, w1, b1)), heads[0][2].p, self.training)            # (S*n, 7*hid)
-        w2 = feat.new_zeros(sum(ks), len(heads) * hid_dim)                                        # block diagonal
-        row = 0
-        for i, (h, k) in enumerate(zip(heads, ks)):
-            w2[row:row + k, i * hid_dim:(i + 1) * hid_dim] = h[3].weight
-            row += k
-        logits = F.linear(hid, w2, torch.cat([h[3].bias for h in heads], 0))                      # (S*n, sum k)
+        if not self.training and not torch.is_grad_enabled():
+            # a frozen model: the stacked parameters are built once (the same ops, the same bits) and reused
+            w1, b1, w2, b2 = scene_tail_ops.stacked_head_params(self, prefix, heads, ks)
+            logits = F.linear(F.relu(F.linear(feat, w1, b1)), w2, b2)
+        else:
+            w1 = torch.cat([h[0].weight for h in heads], 0)
+            b1 = torch.cat([h[0].bias for h in heads], 0)
+            hid = F.dropout(F.relu(F.linear(feat, w1, b1)), heads[0][2].p, self.training)        # (S*n, 7*hid)
+            w2 = feat.new_zeros(sum(ks), len(heads) * hid_dim)                                    # block diagonal
+            row = 0
+            for i, (h, k) in enumerate(zip(heads, ks)):
+                w2[row:row + k, i * hid_dim:(i + 1) * hid_dim] = h[3].weight
+                row += k
+            logits = F.linear(hid, w2, torch.cat([h[3].bias for h in heads], 0))                  # (S*n, sum k)
         n_soft = sum(1 for _, _, kind in _HEAD_SPECS if kind == "softmax" and prefix == "")       # SG_ heads: all sigmoid
         k_soft = sum(ks[:n_soft])
         assert all(k == ks[0] for k in ks[:n_soft])
@@ -960,6 +985,20 @@ class GAR_Fusion_Net3(nn.Module):
 
     def getloss(self, ):
         return
+
+
+def _eval_bn(bn, x):
+    """Eval-mode BatchNorm1d of the batched routes, (x - mean) / sqrt(var + eps) * weight + bias as ever, with the square
+    root cached on the module (keyed on the _version / data_ptr of running_var, like sparse_ops.fold_bn): the same bits, two
+    launches fewer per call on a frozen model."""
+    rv = bn.running_var
+    key = (float(bn.eps), rv._version, rv.data_ptr(), rv.device)
+    cached = bn.__dict__.get("_mgar_eval_std")
+    if cached is None or cached[0] != key:
+        with torch.no_grad():
+            cached = (key, torch.sqrt(rv + bn.eps))
+        bn.__dict__["_mgar_eval_std"] = cached
+    return (x - bn.running_mean) / cached[1] * bn.weight + bn.bias
 
 
 def _giou_batched(bb):

@@ -12,12 +12,12 @@ from . import _lib as L
 from .dafm_ops import scene_offsets
 
 SceneLayout = namedtuple("SceneLayout", "counts rows pairs n_max scene_off de_off row_scene row_slot pair_index diag_index "
-                                        "row_local")
+                                        "row_local mnp")
 SceneLayout.__doc__ = """counts: host tuple; rows = sum n_s; pairs = sum n_s^2; scene_off (S+1) / de_off (S) int32 as for
 dafm_attention; row_scene (rows): scene id of every packed row; row_slot (rows): s * MNP + i, the row's place in a padded
 (S, MNP, .) tensor viewed as (S * MNP, .); pair_index (pairs): (s * MNP + i) * MNP + j, the place of every packed pair in
 (S, MNP, MNP) viewed flat; diag_index (rows): position of every (i, i) in the packed pairs; row_local (rows): s * n_max + i,
-the row's place in a (S, n_max, .) tensor."""
+the row's place in a (S, n_max, .) tensor; mnp: the padded slots per scene the indices were built for."""
 
 _LAYOUT_CACHE = {}
 
@@ -49,7 +49,7 @@ def scene_layout(counts, mnp, device):
         return (torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64)).to(device)
 
     out = SceneLayout(counts, sum(counts), m, n_max, so, do, dev(row_scene), dev(row_slot), dev(pair_index), dev(diag_index),
-                      dev(row_local))
+                      dev(row_local), int(mnp))
     if len(_LAYOUT_CACHE) < 64:
         _LAYOUT_CACHE[key] = out
     return out

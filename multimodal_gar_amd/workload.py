@@ -24,6 +24,7 @@ all-reduced by DistributedDataParallel over RCCL.
 """
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -729,6 +730,79 @@ class ForwardStep(_GraphStep):
         return self._forward(batch)
 
     def capture(self, batch, warmup=2):
+        self._warm_up(batch, warmup)
+        self._out = self._record(lambda: self._forward(batch))
+        return self
+
+    def run(self, batch):
+        if self.graph is None:
+            return self._forward(batch)
+        self._replay(batch)
+        return self._out
+
+
+Inference = namedtuple("Inference", "outputs group_id")
+Inference.__doc__ = """outputs: the 16 zero-padded tensors of GAR_Fusion_Net3.forward; group_id (S, MNP) int32: the social group
+the model predicts for every actor -- the smallest j whose thresholded adjacency a_ij >= 0.5, with a_ii = 1 -- and -1 in the
+padding slots."""
+
+
+def predicted_group_ids(gar, a_list, counts):
+    """The group ids of GAR_Fusion_Net3._predicted_groups for every scene of a returned A_list (S, MNP, MNP), counts[s] valid
+    actors in scene s (host ints) -> (S, MNP) int32, -1 in the padding.  Device ops only."""
+    s, mnp = a_list.shape[0], a_list.shape[1]
+    out = torch.full((s, mnp), -1, dtype=torch.int32, device=a_list.device)
+    for i, n in enumerate(counts):
+        out[i, :n] = gar._predicted_groups(a_list[i, :n, :n]).to(torch.int32)
+    return out
+
+
+class InferStep(_GraphStep):
+    """Eval-mode forward of the clip model: the whole ClipModel in .eval() (running-statistics BatchNorm folded into the
+    kernels' stores, no dropout) under torch.no_grad(), the inference route of every module.  Same interface and precision rule
+    as ForwardStep (capture / run / run_eager, .module, .graph; precision="bf16" converts the frozen I3D's convolution
+    weights once); ``run`` returns Inference(outputs, group_id).  The group ids come from the fused tail kernel
+    (scene_tail_ops) where the fusion net takes it and from _predicted_groups on the returned adjacency otherwise.  No
+    BatchNorm buffer is written.  The voxel route is eager only while voxel_route_capturable() says so: capture() raises."""
+
+    def __init__(self, n_actors, n_points, device, gat=True, route="pointnet2", precision="fp32", seed=2023,
+                 fusion="Attention_mat", modality="Multi"):
+        assert precision in ("fp32", "bf16")
+        torch.manual_seed(seed)
+        self.model = ClipModel(n_actors, n_points, gat, route, fusion, modality).to(device)
+        self.model.eval()
+        self.module = self.model
+        self.precision = precision
+        self.device = device
+        self.route = route
+        if precision == "bf16" and modality != "LiDAR":
+            for m in self.model.net.RGB_backbone.backbone_net.modules():
+                if isinstance(m, nn.Conv3d):
+                    m.weight.data = m.weight.data.to(torch.bfloat16)
+        self._out = None
+
+    def _scene_counts(self, batch):
+        counts = batch.get("actor_counts")
+        if counts is None:
+            return [self.model.n_actors] * (batch["n_clips"] * batch["n_frames"])
+        return _frame_counts(counts, batch["n_frames"])
+
+    def _forward(self, batch):
+        gar = self.model.net.GAR_model
+        with torch.no_grad(), torch.autocast(device_type=self.device.type, dtype=torch.bfloat16, enabled=self.precision == "bf16"):
+            gar._tail_group_id = None
+            outputs = self.model(batch)
+            group_id = gar._tail_group_id
+            if group_id is None:
+                group_id = predicted_group_ids(gar, outputs[0].float(), self._scene_counts(batch))
+        return Inference(tuple(outputs), group_id)
+
+    def run_eager(self, batch):
+        return self._forward(batch)
+
+    def capture(self, batch, warmup=2):
+        if self.route == "voxel" and self.model.modality != "RGB" and not voxel_route_capturable():
+            raise RuntimeError("InferStep.capture: the voxel route is eager only (voxel_route_capturable())")
         self._warm_up(batch, warmup)
         self._out = self._record(lambda: self._forward(batch))
         return self
