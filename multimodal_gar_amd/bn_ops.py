@@ -10,6 +10,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
+from .eval_route import bn_frozen, hooked, needs_grad as _needs_grad
 
 
 def _u8ptr(t):
@@ -352,13 +353,13 @@ def plain_conv(x, conv, want_out_stats=False, bf16_mfma=False):
     an eval-mode BatchNorm follows (the inference route keeps its kernels)."""
     if not (x.is_cuda and x.dtype in _PAYLOADS and x.dim() >= 3 and conv.bias is None):
         return None
-    if x.dtype != torch.float32 and torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
+    if x.dtype != torch.float32 and _needs_grad(x, (conv.weight,)):
         return None
     c, cout = x.shape[1], conv.out_channels
     x3 = x.contiguous().flatten(2)
     if c > PLAIN_CONV_MAX_IN or cout > PLAIN_CONV_MAX_OUT or x3.shape[2] % 4 != 0 or x3.shape[0] * x3.shape[2] < (1 << 16):
         return None
-    needs_grad = torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad)
+    needs_grad = _needs_grad(x, (conv.weight,))
     if bf16_mfma and mlp_bf16_mfma_plan(x3, cout, needs_grad, None, PLAIN_CONV_MAX_IN, PLAIN_CONV_MAX_OUT):
         y = _conv_bf16_mfma(x3, _f32(conv.weight.detach()).view(cout, c), None, None, None, None, False)
         y = y.view(x.shape[0], cout, *x.shape[2:])
@@ -439,14 +440,13 @@ def eval_mlp_plan(x, bn, conv, bn2=None, others=()):
         return None
     mods = [m for m in (bn, conv, bn2) + tuple(others) if m is not None]
     for m in (bn, bn2):
-        if m is not None and not (isinstance(m, _BN_TYPES) and not m.training and m.track_running_stats
-                                  and m.running_mean is not None and m.running_var is not None):
+        if m is not None and not (isinstance(m, _BN_TYPES) and m.track_running_stats and bn_frozen(m)):
             return None
     if not _is_pointwise(conv) or conv.bias is not None:
         return None
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in mods for p in m.parameters(recurse=False))):
+    if _needs_grad(x, (p for m in mods for p in m.parameters(recurse=False))):
         return None
-    if any(m._forward_hooks or m._forward_pre_hooks for m in mods):
+    if hooked(*mods):
         return None
     c, cout = x.shape[1], conv.out_channels
     if conv.in_channels != c or c < 1 or (bn is not None and bn.num_features != c) or (bn2 is not None and bn2.num_features != cout):
@@ -546,16 +546,15 @@ def mlp_bf16_wide_plan(x, conv, bn=None, bn2=None, others=(), pool=False, cin=No
             continue
         if not isinstance(m, _BN_TYPES):
             return False
-        if not m.training and not (MLP_EVAL_FUSE and m.track_running_stats and m.running_mean is not None
-                                   and m.running_var is not None):
+        if not m.training and not (MLP_EVAL_FUSE and m.track_running_stats and bn_frozen(m)):
             return False
     if bn2 is not None and bn2.training:
         return False
     if not _is_pointwise(conv) or conv.bias is not None:
         return False
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in mods for p in m.parameters(recurse=False))):
+    if _needs_grad(x, (p for m in mods for p in m.parameters(recurse=False))):
         return False
-    if any(m._forward_hooks or m._forward_pre_hooks for m in mods):
+    if hooked(*mods):
         return False
     c, cout = x.shape[1], conv.out_channels
     if (conv.in_channels != c if cin is None else cin != c) or (bn is not None and bn.num_features != c) \
@@ -633,7 +632,7 @@ def bn_act_conv(x, bn, relu, conv, rowmajor_grad=False, in_stats=None, want_out_
         return y if y is None or not want_out_stats else (y, None)
     if not (x.is_cuda and x.dtype in _PAYLOADS and bn.training and x.dim() >= 3 and conv.bias is None):
         return None
-    if x.dtype != torch.float32 and torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
+    if x.dtype != torch.float32 and _needs_grad(x, (conv.weight,)):
         return None   # the weight-gradient kernel (csrc/pointwise_dw.hip) takes fp32 payloads only: bf16 is a forward path
     c, cout = x.shape[1], conv.out_channels
     x3 = x.contiguous().flatten(2)
@@ -642,7 +641,7 @@ def bn_act_conv(x, bn, relu, conv, rowmajor_grad=False, in_stats=None, want_out_
         return None
     mean, invstd = _stats(x3, bn, in_stats)
     gamma, beta = _affine(bn, c, x.device)
-    needs_grad = torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or gamma.requires_grad or beta.requires_grad)
+    needs_grad = _needs_grad(x, (conv.weight, gamma, beta))
     if mlp_bf16_mfma_plan(x3, cout, needs_grad, bn):
         y = _conv_bf16_mfma(x3, _f32(conv.weight.detach()).view(cout, c), mean, invstd, gamma.detach(), beta.detach(), relu)
         y = y.view(x.shape[0], cout, *x.shape[2:])
@@ -809,7 +808,7 @@ def bn_act_rows(x, bn, relu):
             and x.shape[0] > 0):
         return None
     dt = x.dtype
-    if dt != torch.float32 and torch.is_grad_enabled() and (x.requires_grad or (bn.affine and bn.weight.requires_grad)):
+    if dt != torch.float32 and _needs_grad(x, (bn.weight,)):
         return None   # the row-major backward (mgar_bn_rows_bwd) takes fp32 payloads only
     x = x.contiguous()
     rows, c = x.shape
@@ -870,7 +869,7 @@ def bn_act(x, bn, relu, rowmajor_grad=False, out=None, in_stats=None, to_channel
     """[relu](bn(x)) for x (B, C, ...) contiguous on the device; ``bn`` is the nn.BatchNormNd module.
     ``out``: write the result into this channel slice of a wider tensor (forward-only callers; see _slice_stride).
     A channels-last 5-D x (forward only) stays channels-last; ``to_channels_last``: NCDHW in, channels-last out."""
-    if x.is_cuda and x.dim() == 5 and not (torch.is_grad_enabled() and (x.requires_grad or (bn.affine and bn.weight.requires_grad))):
+    if x.is_cuda and x.dim() == 5 and not _needs_grad(x, (bn.weight,)):
         y = bn_act_channels_last(x, bn, relu, False, out) if is_channels_last_3d(x) else \
             (bn_act_to_channels_last(x, bn, relu, False) if to_channels_last else None)
         if y is not None:
@@ -878,14 +877,14 @@ def bn_act(x, bn, relu, rowmajor_grad=False, out=None, in_stats=None, to_channel
     x3 = x.contiguous().flatten(2) if x.dim() > 2 else x.contiguous().unsqueeze(-1)
     if not bn.training and torch.is_grad_enabled() and x.requires_grad:
         return None  # eval-mode backward: let the caller take the plain torch path
-    forward_only = not (torch.is_grad_enabled() and (x.requires_grad or (bn.affine and bn.weight.requires_grad)))
+    forward_only = not _needs_grad(x, (bn.weight,))
     if forward_only and bn.training and x.is_cuda and in_stats is None:
         y = _small_fused(x, x3, bn, relu, False, out)
         if y is not None:
             return y
     mean, invstd = _stats(x3, bn, in_stats)
     bstride = _slice_stride(out, x)
-    if bstride is not None and x.dtype in _PAYLOADS and not (torch.is_grad_enabled() and (x.requires_grad or bn.weight.requires_grad)):
+    if bstride is not None and x.dtype in _PAYLOADS and forward_only:
         return _apply_into(x3, bn, relu, mean, invstd, False, out, bstride)
     gamma, beta = _affine(bn, x3.shape[1], x.device)
     return _BnAct.apply(x3, gamma, beta, mean, invstd, relu, rowmajor_grad).view(x.shape)
@@ -895,8 +894,7 @@ def bn_act_per_sample(x, bn, relu, out=None, to_channels_last=False):
     """[relu](bn(x)) where every sample of x (G, C, ...) is normalised with its own batch statistics and the running
     statistics get the G momentum updates in sample order: G clips through a train-mode BatchNorm in ONE pass, with
     the result of feeding them one at a time.  Forward only (frozen I3D); None if that does not apply."""
-    if not (x.is_cuda and x.dtype in _PAYLOADS and bn.training and x.dim() >= 3) or (torch.is_grad_enabled() and
-                                                                                        (x.requires_grad or bn.weight.requires_grad)):
+    if not (x.is_cuda and x.dtype in _PAYLOADS and bn.training and x.dim() >= 3) or _needs_grad(x, (bn.weight,)):
         return None
     if x.dim() == 5:
         y = bn_act_channels_last(x, bn, relu, True, out) if is_channels_last_3d(x) else \

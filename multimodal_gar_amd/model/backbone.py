@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..eval_route import bn_frozen, cached, needs_grad
 from ..nn_utils import PointwiseSequential, conv1x1
 
 
@@ -46,7 +47,7 @@ class MaxPool3dSamePadding(nn.MaxPool3d):
         return sum(_same_pad_1d(s, self.kernel_size[dim], self.stride[dim]))
 
     def forward(self, x):
-        if x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and not (torch.is_grad_enabled() and x.requires_grad):
+        if x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and not needs_grad(x):
             # forward-only fused kernel (csrc/maxpool3d.hip): no padded copy, no index tensor; fp32 or bf16 payload
             from .. import _lib as L
             n, c, t, h, w = x.shape
@@ -114,141 +115,136 @@ class Unit3D(nn.Module):
 
     stem_kernel = True     # 3 -> 64, 7x7x7, stride 2 on the device: csrc/stem_conv.hip instead of pad + library convolution
 
+    # The four kernels of the unit's own (_own_route, _launch).  Each predicate reads attributes of x and of the unit only: no
+    # tensor is touched.
     def _stem_route(self, x):
-        """_stem_conv takes x (attributes of x and of the unit only: no tensor is touched)"""
+        """the I3D stem (Conv3d_1a_7x7) on csrc/stem_conv.hip takes x: "same" padding inside the kernel, NCDHW in and out"""
         c = self.conv3d
         return bool(self.stem_kernel and x.is_cuda and x.dim() == 5 and x.dtype in (torch.float32, torch.bfloat16)
                     and c.in_channels == 3 and c.out_channels == 64 and self._kernel_shape == (7, 7, 7) and self._stride == (2, 2, 2)
-                    and c.bias is None and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad)))
-
-    def _stem_conv(self, x):
-        """The I3D stem (Conv3d_1a_7x7) on csrc/stem_conv.hip: "same" padding inside the kernel, NCDHW in and out; or None."""
-        c = self.conv3d
-        if not self._stem_route(x):
-            return None
-        from .. import _lib as L
-        if torch.is_autocast_enabled() and x.dtype == torch.float32:
-            x = x.to(torch.get_autocast_dtype('cuda'))
-        x = x.contiguous()
-        n, _, t, h, w = x.shape
-        y = torch.empty((n, 64, (t + 1) // 2, (h + 1) // 2, (w + 1) // 2), dtype=x.dtype, device=x.device)
-        wp = torch.empty((L.raw("mgar_stem_conv3d_workspace_floats"),), dtype=torch.float32, device=x.device)
-        wf = c.weight.detach().float().contiguous()
-        L.payload_call("mgar_stem_conv3d_fwd", x.dtype, L.pptr(x, x.dtype), n, t, h, w, L.fptr(wf), L.fptr(wp), L.pptr(y, x.dtype),
-                       L.stream_of(x))
-        return y
+                    and c.bias is None and not needs_grad(x, (c.weight,)))
 
     gemm_1x1 = os.environ.get("MGAR_I3D_GEMM_1X1", "1") != "0"        # 1x1x1 units on the device: library GEMMs (one per sample) instead of the library convolution; bf16 payloads: k1_bf16 below
     wino_kernel = os.environ.get("MGAR_I3D_OWN_CONV", "1") != "0"     # 3x3x3, stride 1 on the device: csrc/conv3d_wino.hip (Winograd F(2,3) along W on the fp32 MFMA); bf16 payloads: csrc/conv3d_bf16.hip (direct, bf16 MFMA)
 
+    def _k3_route(self, x):
+        """the 3x3x3 / stride-1 units (Conv3d_2c_3x3, every Mixed block's Conv3d_0b_3x3) on csrc/conv3d_wino.hip take x: "same"
+        padding inside the kernel, NCDHW in and out, fp32, forward only"""
+        c = self.conv3d
+        return bool(self.wino_kernel and x.is_cuda and x.dim() == 5 and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+                    and self._kernel_shape == (3, 3, 3) and self._stride == (1, 1, 1) and c.bias is None and c.groups == 1
+                    and c.in_channels % 2 == 0 and x.shape[4] % 2 == 0 and x.is_contiguous() and c.weight.dtype == torch.float32
+                    and not needs_grad(x, (c.weight,)))
+
     def _k3_bf16_route(self, x):
-        """_k3_conv_bf16 takes x (attributes only)"""
+        """the same units on bf16 payloads (the bf16 forward configurations, autocast on or off): csrc/conv3d_bf16.hip, a direct
+        convolution on the bf16 MFMA, bf16 NCDHW in and out; the weight (bf16 as ForwardStep converts it, or fp32) goes in as fp32
+        and is rounded to bf16 when the kernel packs it, as in the stem"""
         c = self.conv3d
         return bool(self.wino_kernel and x.is_cuda and x.dim() == 5 and x.dtype == torch.bfloat16
                     and self._kernel_shape == (3, 3, 3) and self._stride == (1, 1, 1) and c.bias is None and c.groups == 1
                     and c.in_channels % 8 == 0 and x.shape[4] % 2 == 0 and x.is_contiguous()
                     and c.weight.dtype in (torch.bfloat16, torch.float32)
-                    and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad)))
+                    and not needs_grad(x, (c.weight,)))
 
-    def _k3_route(self, x):
-        """the fp32 kernel of _k3_conv takes x (attributes only)"""
-        c = self.conv3d
-        return bool(self.wino_kernel and x.is_cuda and x.dim() == 5 and x.dtype == torch.float32 and not torch.is_autocast_enabled()
-                    and self._kernel_shape == (3, 3, 3) and self._stride == (1, 1, 1) and c.bias is None and c.groups == 1
-                    and c.in_channels % 2 == 0 and x.shape[4] % 2 == 0 and x.is_contiguous() and c.weight.dtype == torch.float32
-                    and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad)))
+    k1_bf16 = os.environ.get("MGAR_I3D_K1_BF16", "0") != "0"          # 1x1x1 units on bf16 payloads: the 1x1x1 entry point of csrc/pointwise_wide_bf16.hip (bf16 MFMA, one launch for all samples) instead of the per-sample library GEMMs; inside gemm_1x1.  Off by default: c2's step did not clear the bar (DESIGN.md section 3.13b1d)
 
-    def _k3_conv_bf16(self, x):
-        """bf16 payloads (the bf16 forward configurations, autocast on or off): csrc/conv3d_bf16.hip, a direct convolution on the
-        bf16 MFMA, bf16 NCDHW in and out; the weight (bf16 as ForwardStep converts it, or fp32) goes in as fp32 and is rounded to
-        bf16 when the kernel packs it, as in _stem_conv.  Or None."""
-        c = self.conv3d
-        if not self._k3_bf16_route(x):
-            return None
-        from .. import _lib as L
-        n, cin, d, h, w = x.shape
-        y = torch.empty((n, c.out_channels, d, h, w), dtype=torch.bfloat16, device=x.device)
-        wp = torch.empty((L.raw("mgar_conv3d_k3_bf16_workspace_bytes", cin, c.out_channels),), dtype=torch.uint8, device=x.device)
-        wf = c.weight.detach().float().contiguous()
-        L.call("mgar_conv3d_k3_bf16_fwd", L.pptr(x, torch.bfloat16), n, cin, d, h, w, L.fptr(wf), c.out_channels, wp.data_ptr(),
-               L.pptr(y, torch.bfloat16), L.stream_of(x))
-        return y
-
-    def _k3_conv(self, x):
-        """The 3x3x3 / stride-1 units (Conv3d_2c_3x3, every Mixed block's Conv3d_0b_3x3) on csrc/conv3d_wino.hip: "same"
-        padding inside the kernel, NCDHW in and out, fp32, forward only; bf16 inputs: _k3_conv_bf16; or None (the library
-        convolution then)."""
-        c = self.conv3d
-        if x.dtype == torch.bfloat16:
-            return self._k3_conv_bf16(x)
-        if not self._k3_route(x):
-            return None
-        from .. import _lib as L
-        n, cin, d, h, w = x.shape
-        y = torch.empty((n, c.out_channels, d, h, w), dtype=torch.float32, device=x.device)
-        wp = torch.empty((L.raw("mgar_conv3d_k3_workspace_floats", cin, c.out_channels),), dtype=torch.float32, device=x.device)
-        wf = c.weight.detach().contiguous()
-        L.call("mgar_conv3d_k3_fwd", L.fptr(x), n, cin, d, h, w, L.fptr(wf), c.out_channels, L.fptr(wp), L.fptr(y), L.stream_of(x))
-        return y
-
-    k1_bf16 = os.environ.get("MGAR_I3D_K1_BF16", "0") != "0"          # 1x1x1 units on bf16 payloads: mgar_conv1x1_bf16_fwd of csrc/pointwise_wide_bf16.hip (bf16 MFMA, one launch for all samples) instead of the per-sample library GEMMs; inside gemm_1x1.  Off by default: c2's step did not clear the bar (DESIGN.md section 3.13b1d)
-
-    K1_MAX_IN, K1_MAX_OUT = 1024, 512                                   # mgar_conv1x1_bf16_fwd's channel range
+    K1_MAX_IN, K1_MAX_OUT = 1024, 512                                   # the 1x1x1 kernel's channel range
 
     def _k1_bf16_route(self, x):
-        """_k1_conv_bf16 takes x (attributes only)"""
+        """a 1x1x1 unit on bf16 payloads (autocast on or off) as ONE launch of csrc/pointwise_wide_bf16.hip for all samples takes
+        x: bf16 NCDHW in and out, the weight as in _k3_bf16_route"""
         c = self.conv3d
         return bool(self.gemm_1x1 and self.k1_bf16 and x.is_cuda and x.dim() == 5 and x.dtype == torch.bfloat16 and x.is_contiguous()
                     and self._kernel_shape == (1, 1, 1) and self._stride == (1, 1, 1) and c.groups == 1 and c.bias is None
                     and c.weight.dtype in (torch.bfloat16, torch.float32)
                     and (x.shape[2] * x.shape[3] * x.shape[4]) % 4 == 0
                     and 1 <= c.in_channels <= self.K1_MAX_IN and 1 <= c.out_channels <= self.K1_MAX_OUT
-                    and not (torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad)))
+                    and not needs_grad(x, (c.weight,)))
 
     def _k1_weight(self):
-        """The (Cout, Cin) fp32 weight mgar_conv1x1_bf16_fwd reads (a bf16 weight widened exactly; the kernel rounds to bf16), cached
-        on the unit and keyed on the weight's data_ptr and _version as sparse_ops.fold_bn keys its result: the frozen trunk launches
-        no conversion per call, an in-place update or a replaced .data recomputes."""
-        w = self.conv3d.weight
-        key = (w.data_ptr(), w._version, w.device, w.dtype)
-        cached = self.__dict__.get("_mgar_k1_weight")
-        if cached is None or cached[0] != key:
-            with torch.no_grad(), torch.autocast(device_type=w.device.type, enabled=False):
-                wf = w.detach().reshape(self.conv3d.out_channels, self.conv3d.in_channels).float().contiguous()
-            cached = (key, wf)
-            self.__dict__["_mgar_k1_weight"] = cached
-        return cached[1]
+        """The (Cout, Cin) fp32 weight the 1x1x1 kernel reads (a bf16 weight widened exactly; the kernel rounds to bf16), cached
+        on the unit (eval_route.cached): the frozen trunk launches no conversion per call, an in-place update or a replaced .data
+        recomputes."""
+        c = self.conv3d
+        return cached(self, "_mgar_k1_weight", (c.weight,),
+                      lambda: c.weight.detach().reshape(c.out_channels, c.in_channels).float().contiguous())
 
-    def _k1_conv_bf16(self, x):
-        """bf16 payloads (autocast on or off): the unit as ONE launch of mgar_conv1x1_bf16_fwd[_affine] (csrc/pointwise_wide_bf16.hip) for all samples, bf16 NCDHW in and
-        out, the weight as in _k3_conv_bf16.  Or None."""
-        if not self._k1_bf16_route(x):
-            return None
+    def _own_route(self, x):
+        """Which of the unit's own kernels takes x: 'stem', 'k3', 'k3_bf16', 'k1_bf16' -- or None (the library).  Pure.  Every
+        predicate names its kernel shape, so at most one family is asked (this runs three times per eager forward)."""
+        k = self._kernel_shape
+        if k == (1, 1, 1):
+            return 'k1_bf16' if self._k1_bf16_route(x) else None
+        if k == (3, 3, 3):
+            if self._k3_route(x):
+                return 'k3'
+            return 'k3_bf16' if self._k3_bf16_route(x) else None
+        return 'stem' if k == (7, 7, 7) and self._stem_route(x) else None
+
+    def _launch(self, x, route, epilogue=None, out=None):
+        """conv(x) on the kernel of ``route`` (_own_route) -- the plain entry point -- or, with epilogue = (scale, shift, relu),
+        [relu](scale * conv(x) + shift) in the kernel's store -- the *_affine one.  ``out``: a channel slice of a wider tensor the
+        store can address (_conv_folded checks), 3x3x3 and 1x1x1 units with an epilogue only; a fresh tensor otherwise."""
         from .. import _lib as L
         c = self.conv3d
+        if route == 'stem':
+            if torch.is_autocast_enabled() and x.dtype == torch.float32:
+                x = x.to(torch.get_autocast_dtype('cuda'))
+            x = x.contiguous()
         n, cin, d, h, w = x.shape
-        p = d * h * w
-        y = torch.empty((n, c.out_channels, d, h, w), dtype=torch.bfloat16, device=x.device)
-        L.call("mgar_conv1x1_bf16_fwd", L.pptr(x, torch.bfloat16), n, cin, p, L.fptr(self._k1_weight()), c.out_channels,
-               L.pptr(y, torch.bfloat16), c.out_channels * p, L.stream_of(x))
+        dt, cout, st = x.dtype, c.out_channels, L.stream_of(x)
+        affine = epilogue is not None
+        post = (L.fptr(epilogue[0]), L.fptr(epilogue[1]), epilogue[2]) if affine else ()
+        if route == 'stem':
+            y = torch.empty((n, 64, (d + 1) // 2, (h + 1) // 2, (w + 1) // 2), dtype=dt, device=x.device)
+            wp = torch.empty((L.raw("mgar_stem_conv3d_workspace_floats"),), dtype=torch.float32, device=x.device)
+            wf = c.weight.detach().float().contiguous()
+            args = (L.pptr(x, dt), n, d, h, w, L.fptr(wf), L.fptr(wp)) + post + (L.pptr(y, dt), st)
+            if affine:
+                L.call("mgar_stem_conv3d_fwd_affine" if dt == torch.float32 else "mgar_stem_conv3d_bf16_fwd_affine", *args)
+            else:
+                L.payload_call("mgar_stem_conv3d_fwd", dt, *args)
+            return y
+        assert out is None or (affine and out.dtype == dt), "only the *_affine entry points address a slice, of x's dtype"
+        if out is None:
+            y = torch.empty((n, cout, d, h, w), dtype=dt, device=x.device)
+            dst = post + (L.pptr(y, dt), cout * d * h * w, st)
+        else:
+            y, dst = out, post + (out.data_ptr(), out.stride(0), st)
+        if route == 'k1_bf16':
+            L.call("mgar_conv1x1_bf16_fwd_affine" if affine else "mgar_conv1x1_bf16_fwd", L.pptr(x, torch.bfloat16), n, cin, d * h * w,
+                   L.fptr(self._k1_weight()), cout, *dst)
+            return y
+        if not affine:
+            dst = (L.pptr(y, dt), st)                       # the plain 3x3x3 entry points take no batch stride
+        if route == 'k3':
+            wp = torch.empty((L.raw("mgar_conv3d_k3_workspace_floats", cin, cout),), dtype=torch.float32, device=x.device)
+            wf = c.weight.detach().contiguous()
+            L.call("mgar_conv3d_k3_fwd_affine" if affine else "mgar_conv3d_k3_fwd", L.fptr(x), n, cin, d, h, w, L.fptr(wf), cout,
+                   L.fptr(wp), *dst)
+        else:
+            wp = torch.empty((L.raw("mgar_conv3d_k3_bf16_workspace_bytes", cin, cout),), dtype=torch.uint8, device=x.device)
+            wf = c.weight.detach().float().contiguous()
+            L.call("mgar_conv3d_k3_bf16_fwd_affine" if affine else "mgar_conv3d_k3_bf16_fwd", L.pptr(x, torch.bfloat16), n, cin, d, h, w,
+                   L.fptr(wf), cout, wp.data_ptr(), *dst)
         return y
 
+    def _k3_conv(self, x):
+        """conv(x) where a 3x3x3 kernel of the unit's own takes x (fp32 or bf16), else None: what the device tests probe"""
+        route = self._own_route(x)
+        return self._launch(x, route) if route in ('k3', 'k3_bf16') else None
+
     def _conv(self, x):
+        route = self._own_route(x)
+        if route is not None:
+            return self._launch(x, route)
         pads = _same_pads(x.shape[2:], self._kernel_shape, self._stride)
-        stem = self._stem_conv(x)
-        if stem is not None:
-            return stem
-        k3 = self._k3_conv(x)
-        if k3 is not None:
-            return k3
-        k1 = self._k1_conv_bf16(x)
-        if k1 is not None:
-            return k1
         if (self.gemm_1x1 and x.is_cuda and x.dim() == 5 and self._kernel_shape == (1, 1, 1) and self._stride == (1, 1, 1)
                 and x.is_contiguous() and self.conv3d.groups == 1
                 and (not torch.is_autocast_enabled() or x.dtype == torch.bfloat16)     # operands already bf16: nothing for autocast to cast (out= GEMMs are not re-cast)
                 and x.dtype == self.conv3d.weight.dtype
-                and not (torch.is_grad_enabled() and (x.requires_grad or self.conv3d.weight.requires_grad))):
+                and not needs_grad(x, (self.conv3d.weight,))):
             # a 1x1x1 convolution is the GEMM W (C_out, C_in) x (C_in, T*H*W) per sample, on the NCDHW tensor as it lies (MIOpen
             # wraps its NDHWC kernels in two layout transposes and needs a find pass per shape).  One plain GEMM per sample, not one
             # strided-batched call: with 5 clips per pass the batched route hung the two-stream graph replay in 2 of 4 runs (4 of 4
@@ -273,10 +269,7 @@ class Unit3D(nn.Module):
         """gamma > 0 in every channel (what makes relu(bn(.)) monotone non-decreasing); one host read per weight version --
         the frozen I3D's weights never change, and the first call happens in an eager warm-up step, never inside a capture."""
         w = self.bn.weight
-        key = (w.data_ptr(), w._version)
-        if getattr(self, "_gamma_pos_key", None) != key:
-            self._gamma_pos_key, self._gamma_pos = key, bool((w.detach() > 0).all().item())
-        return self._gamma_pos
+        return cached(self, "_mgar_gamma_pos", (w,), lambda: bool((w.detach() > 0).all().item()))
 
     def forward_then_pool(self, x, pool):
         """pool(self(x)) for a MaxPool3dSamePadding ``pool`` that directly follows this unit (reference model/backbone.py:305-313:
@@ -287,9 +280,9 @@ class Unit3D(nn.Module):
         stem) -- one read + one write of z less (7.6 GB of the stem's output per c3 step)."""
         if not (self.pool_first and self._use_batch_norm and self._activation_fn is F.relu and self.bn.training and self.bn.affine
                 and x.is_cuda and x.dim() == 5 and not self.emit_channels_last
-                and not (torch.is_grad_enabled() and (x.requires_grad or self.bn.weight.requires_grad))):
+                and not needs_grad(x, (self.bn.weight,))):
             return None
-        if torch.cuda.is_current_stream_capturing() and getattr(self, "_gamma_pos_key", None) is None:
+        if torch.cuda.is_current_stream_capturing() and "_mgar_gamma_pos" not in self.__dict__:   # not primed before this capture
             return None
         if not self._gamma_positive():
             return None
@@ -318,18 +311,13 @@ class Unit3D(nn.Module):
                 and not self.emit_channels_last):
             return False
         bn = self.bn
-        if bn.training or not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
-            return False
-        if torch.is_grad_enabled() and (x.requires_grad or self.conv3d.weight.requires_grad
-                                        or (bn.affine and (bn.weight.requires_grad or bn.bias.requires_grad))):
-            return False
-        return True
+        return bool(bn.track_running_stats and bn_frozen(bn) and not needs_grad(x, (self.conv3d.weight, bn.weight, bn.bias)))
 
     def eval_fold_plan_1x1(self, x):
-        """'k1_bf16' where a 1x1x1 unit runs on x as one launch of mgar_conv1x1_bf16_fwd_affine -- eval_fold_plan's conditions on
-        the BatchNorm, the activation, gradients and emit_channels_last, plus _k1_bf16_route(x) -- or None.  Pure.  forward
-        consults it where eval_fold_plan (which never folds a 1x1x1 unit) returns None."""
-        return 'k1_bf16' if self._eval_foldable(x) and self._k1_bf16_route(x) else None
+        """'k1_bf16' where a 1x1x1 unit runs on x as one launch of the 1x1x1 kernel's affine entry point -- eval_fold_plan's
+        conditions on the BatchNorm, the activation, gradients and emit_channels_last, plus _k1_bf16_route(x) -- or None.  Pure.
+        forward consults it where eval_fold_plan (which never folds a 1x1x1 unit) returns None."""
+        return 'k1_bf16' if self._own_route(x) == 'k1_bf16' and self._eval_foldable(x) else None
 
     def eval_fold_plan(self, x):
         """Which *_affine entry point runs this unit on x in one launch: 'stem', 'k3' (fp32) or 'k3_bf16' -- or None for the
@@ -337,59 +325,23 @@ class Unit3D(nn.Module):
         on, the BatchNorm is in eval mode with running statistics, the activation is ReLU or none, nothing asks for a gradient
         (input, convolution weight, BatchNorm affine parameters), the unit does not emit channels-last, and the unit's own
         convolution kernel takes x (_stem_route / _k3_route / _k3_bf16_route); 1x1x1 units never are."""
-        if not self._eval_foldable(x):
-            return None
-        if self._stem_route(x):
-            return 'stem'
-        if x.dtype == torch.bfloat16:
-            return 'k3_bf16' if self._k3_bf16_route(x) else None
-        return 'k3' if self._k3_route(x) else None
+        route = self._own_route(x)                           # the cheaper question first: most units are 1x1x1
+        return route if route not in (None, 'k1_bf16') and self._eval_foldable(x) else None
 
     def _conv_folded(self, x, route, out):
         """One call of the route's *_affine entry point: [relu](bn(conv(x))) with bn as sparse_ops.fold_bn's cached (scale, shift).
         A 3x3x3 or 1x1x1 unit writes into ``out`` where that is a channel slice of a wider contiguous tensor (bn_ops._slice_stride)
         the kernel's store can address (even batch stride; fp32: 8-byte aligned pairs; 1x1x1: batch stride % 4 == 0 and an 8-byte
         aligned base); into a fresh tensor otherwise."""
-        from .. import _lib as L, bn_ops, sparse_ops
-        c = self.conv3d
-        scale, shift = sparse_ops.fold_bn(self.bn)
-        relu = int(self._activation_fn is F.relu)
-        if route == 'stem':
-            if torch.is_autocast_enabled() and x.dtype == torch.float32:
-                x = x.to(torch.get_autocast_dtype('cuda'))
-            x = x.contiguous()
-            n, _, t, h, w = x.shape
-            y = torch.empty((n, 64, (t + 1) // 2, (h + 1) // 2, (w + 1) // 2), dtype=x.dtype, device=x.device)
-            wp = torch.empty((L.raw("mgar_stem_conv3d_workspace_floats"),), dtype=torch.float32, device=x.device)
-            wf = c.weight.detach().float().contiguous()
-            name = "mgar_stem_conv3d_fwd_affine" if x.dtype == torch.float32 else "mgar_stem_conv3d_bf16_fwd_affine"
-            L.call(name, L.pptr(x, x.dtype), n, t, h, w, L.fptr(wf), L.fptr(wp), L.fptr(scale), L.fptr(shift), relu, L.pptr(y, x.dtype),
-                   L.stream_of(x))
-            return y
-        n, cin, d, h, w = x.shape
-        dt, cout = x.dtype, c.out_channels
-        bstride = bn_ops._slice_stride(out, _Like((n, cout, d, h, w), dt))
-        if bstride is not None and (bstride % 2 != 0 or out.data_ptr() % (8 if dt == torch.float32 else 2) != 0):
+        from .. import bn_ops, sparse_ops
+        n, _, d, h, w = x.shape
+        bstride = None if route == 'stem' else bn_ops._slice_stride(out, _Like((n, self.conv3d.out_channels, d, h, w), x.dtype))
+        if bstride is not None and (bstride % 2 != 0 or out.data_ptr() % (8 if x.dtype == torch.float32 else 2) != 0):
             bstride = None
         if route == 'k1_bf16' and bstride is not None and (bstride % 4 != 0 or out.data_ptr() % 8 != 0):
             bstride = None                                  # 8-byte stores: the slice starts on one and every sample does
-        y = out if bstride is not None else torch.empty((n, cout, d, h, w), dtype=dt, device=x.device)
-        if bstride is None:
-            bstride = cout * d * h * w
-        if route == 'k1_bf16':
-            L.call("mgar_conv1x1_bf16_fwd_affine", L.pptr(x, torch.bfloat16), n, cin, d * h * w, L.fptr(self._k1_weight()), cout,
-                   L.fptr(scale), L.fptr(shift), relu, y.data_ptr(), bstride, L.stream_of(x))
-        elif route == 'k3':
-            wp = torch.empty((L.raw("mgar_conv3d_k3_workspace_floats", cin, cout),), dtype=torch.float32, device=x.device)
-            wf = c.weight.detach().contiguous()
-            L.call("mgar_conv3d_k3_fwd_affine", L.fptr(x), n, cin, d, h, w, L.fptr(wf), cout, L.fptr(wp), L.fptr(scale), L.fptr(shift),
-                   relu, y.data_ptr(), bstride, L.stream_of(x))
-        else:
-            wp = torch.empty((L.raw("mgar_conv3d_k3_bf16_workspace_bytes", cin, cout),), dtype=torch.uint8, device=x.device)
-            wf = c.weight.detach().float().contiguous()
-            L.call("mgar_conv3d_k3_bf16_fwd_affine", L.pptr(x, torch.bfloat16), n, cin, d, h, w, L.fptr(wf), cout, wp.data_ptr(),
-                   L.fptr(scale), L.fptr(shift), relu, y.data_ptr(), bstride, L.stream_of(x))
-        return y
+        scale, shift = sparse_ops.fold_bn(self.bn)
+        return self._launch(x, route, (scale, shift, int(self._activation_fn is F.relu)), out if bstride is not None else None)
 
     def forward(self, x, out=None):
         """``out`` (optional): a channel slice y[:, c0:c1] of a wider tensor the result should land in (the caller's
@@ -437,7 +389,7 @@ class InceptionModule(nn.Module):
         self.name = name
 
     def forward(self, x):
-        if x.is_cuda and not (torch.is_grad_enabled() and x.requires_grad):
+        if x.is_cuda and not needs_grad(x):
             # frozen backbone on the device: every branch's last BatchNorm + ReLU writes its channels of the concatenated
             # output directly (csrc/bn_act.hip, mgar_bn_act_fwd_into): the torch.cat pass (a read and a write of the whole
             # module output, 3.6 ms per step at config c3) disappears

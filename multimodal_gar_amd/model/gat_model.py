@@ -33,6 +33,7 @@ from .backbone import *  # noqa: F401,F403  (the reference re-exports backbone t
 from .backbone import InceptionI3d, NLBlockND
 from .. import vision_ops as TO
 from .. import graph_ops as pyg_nn
+from ..eval_route import cached
 from ..metric_ops import pairwise_cosine_similarity, pairwise_euclidean_distance
 from ..nonlocal_ops import nl_eval_plan
 from ..dafm_ops import dafm_attention, dafm_attention_add, packed_pairs, scene_offsets
@@ -989,16 +990,11 @@ class GAR_Fusion_Net3(nn.Module):
 
 def _eval_bn(bn, x):
     """Eval-mode BatchNorm1d of the batched routes, (x - mean) / sqrt(var + eps) * weight + bias as ever, with the square
-    root cached on the module (keyed on the _version / data_ptr of running_var, like sparse_ops.fold_bn): the same bits, two
-    launches fewer per call on a frozen model."""
+    root cached on the module (eval_route.cached under running_var, with eps in the key): the same bits, two launches fewer
+    per call on a frozen model."""
     rv = bn.running_var
-    key = (float(bn.eps), rv._version, rv.data_ptr(), rv.device)
-    cached = bn.__dict__.get("_mgar_eval_std")
-    if cached is None or cached[0] != key:
-        with torch.no_grad():
-            cached = (key, torch.sqrt(rv + bn.eps))
-        bn.__dict__["_mgar_eval_std"] = cached
-    return (x - bn.running_mean) / cached[1] * bn.weight + bn.bias
+    std = cached(bn, "_mgar_eval_std", (rv,), lambda: torch.sqrt(rv + bn.eps), extra=(float(bn.eps),))
+    return (x - bn.running_mean) / std * bn.weight + bn.bias
 
 
 def _giou_batched(bb):

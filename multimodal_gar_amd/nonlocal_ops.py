@@ -12,14 +12,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .eval_route import bn_frozen, cached, hooked, needs_grad
 from .nn_utils import _BN_TYPES, _is_pointwise
 
 NL_EVAL_FUSE = os.environ.get("MGAR_NL_EVAL_FUSE", "1") != "0"
 _ENTRY = {torch.float32: "mgar_nonlocal_dot_eval_fwd", torch.bfloat16: "mgar_nonlocal_dot_eval_bf16_fwd"}
-
-
-def _hooked(module):
-    return bool(module._forward_hooks or module._forward_pre_hooks)
 
 
 def _parts(block):
@@ -53,11 +50,11 @@ def nl_eval_refusal(block, x, rows=False):
     if parts is None:
         return "structure"
     bn = parts[4]
-    if bn is not None and (bn.training or bn.running_mean is None or bn.running_var is None):
+    if bn is not None and not bn_frozen(bn):
         return "batch norm"
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in block.parameters())):
+    if needs_grad(x, block.parameters()):
         return "gradient"
-    if _hooked(block.W_z) or any(_hooked(m) for m in parts if m is not None):
+    if hooked(block.W_z, *[m for m in parts if m is not None]):
         return "hook"
     c, p = (x.shape[2], x.shape[1]) if rows else (x.shape[1], math.prod(x.shape[2:]))
     if c != block.in_channels or not L.raw("mgar_nonlocal_dot_eval_supported", c, block.inter_channels, p):
@@ -77,28 +74,25 @@ def nl_eval_plan(block, x, rows=False):
 
 def _params(block, parts):
     """(w_tpg (3 Ci, C), b_tpg (3 Ci), w_z (C, Ci), b_z (C), scale (C), shift (C)), fp32 on the parameters' device: device ops
-    only, no host synchronisation.  Cached on the block, keyed on the _version / data_ptr of every tensor read and on the
-    identity of fold_bn's own cached pair: a frozen model builds them once, an in-place update of any tensor rebuilds them."""
+    only, no host synchronisation.  Cached on the block (eval_route.cached) under every tensor read, derived from fold_bn's own
+    cached pair: a frozen model builds them once, an in-place update of any tensor rebuilds them."""
     from .sparse_ops import fold_bn
     theta, phi, g, conv_z, bn = parts
     read = [m.weight for m in (theta, phi, g, conv_z)] + [m.bias for m in (theta, phi, g, conv_z) if m.bias is not None]
     fold = fold_bn(bn) if bn is not None else (None, None)
-    key = tuple((t._version, t.data_ptr(), t.device) for t in read) + (id(fold[0]), id(fold[1]))
-    cached = block.__dict__.get("_mgar_nl_eval")
-    if cached is not None and cached[0] == key:
-        return cached[1]
     ci, c, dev = block.inter_channels, block.in_channels, conv_z.weight.device
-    with torch.no_grad(), torch.autocast(device_type=dev.type, enabled=False):
-        def bias(m):
-            return m.bias.detach().float() if m.bias is not None else torch.zeros(m.out_channels, dtype=torch.float32, device=dev)
+
+    def bias(m):
+        return m.bias.detach().float() if m.bias is not None else torch.zeros(m.out_channels, dtype=torch.float32, device=dev)
+
+    def build():
         w_tpg = torch.cat([m.weight.detach().float().reshape(ci, c) for m in (theta, phi, g)]).contiguous()
         b_tpg = torch.cat([bias(m) for m in (theta, phi, g)]).contiguous()
         w_z, b_z = conv_z.weight.detach().float().reshape(c, ci).contiguous(), bias(conv_z).contiguous()
         scale, shift = fold if bn is not None else (torch.ones(c, dtype=torch.float32, device=dev),
                                                     torch.zeros(c, dtype=torch.float32, device=dev))
-    params = (w_tpg, b_tpg, w_z, b_z, scale, shift)
-    block.__dict__["_mgar_nl_eval"] = (key, params, fold)     # fold held: its ids stay its own while cached
-    return params
+        return w_tpg, b_tpg, w_z, b_z, scale, shift
+    return cached(block, "_mgar_nl_eval", read, build, derived_from=fold)
 
 
 def nonlocal_dot_eval_fwd(x, strides, n, c, ci, p, params, z):

@@ -11,6 +11,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
+from ....eval_route import needs_grad
 from ...utils.spconv_utils import spconv
 
 
@@ -61,7 +62,7 @@ class VoxelBackBone8x(nn.Module):
         if not (sparse_ops.SPCONV_BF16 and feats.is_cuda and feats.dtype == torch.float32 and torch.is_autocast_enabled()
                 and torch.get_autocast_dtype("cuda") == torch.bfloat16):
             return False
-        return not (torch.is_grad_enabled() and (feats.requires_grad or any(p.requires_grad for p in self.parameters())))
+        return not needs_grad(feats, self.parameters())
 
     def forward(self, batch_dict):
         """voxel_features (V, C), voxel_coords (V, 4) [b, z, y, x] -> encoded_spconv_tensor + multi-scale features."""

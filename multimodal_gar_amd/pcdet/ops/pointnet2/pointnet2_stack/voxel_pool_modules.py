@@ -15,6 +15,7 @@ from torch.autograd.function import once_differentiable
 
 from . import pointnet2_stack_cuda as pointnet2
 from . import voxel_query_utils
+from .....eval_route import bn_frozen, cached, hooked, needs_grad
 from .....nn_utils import PointwiseSequential, _is_pointwise
 
 
@@ -94,10 +95,6 @@ MGAR_VRP_EVAL_FUSE = os.environ.get("MGAR_VRP_EVAL_FUSE", "1") != "0"
 _EVAL_MAXC = 32     # channels = lanes of a half-wave, on both sides of mlps_out
 
 
-def _hooked(module):
-    return bool(module._forward_hooks or module._forward_pre_hooks)
-
-
 def _conv_bn(seq, conv_type, bn_type, n_allowed):
     """(conv, bn) of a [point-wise conv, BatchNorm(, ReLU)] container, or None"""
     mods = list(seq)
@@ -131,13 +128,12 @@ def eval_fuse_plan(module, k, features, xyz):
     if not (pos_conv.in_channels == 3 and pos_conv.out_channels == chans and conv_out.in_channels == chans
             and conv_in.in_channels == features.shape[1] and chans <= _EVAL_MAXC and conv_out.out_channels <= _EVAL_MAXC):
         return None
-    for bn in (bn_in, pos_bn, bn_out):
-        if bn.training or bn.running_mean is None or bn.running_var is None:
-            return None
-    mods = [m for seq in seqs for m in seq]
-    if torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for m in mods for p in m.parameters())):
+    if not all(bn_frozen(bn) for bn in (bn_in, pos_bn, bn_out)):
         return None
-    if any(_hooked(m) for m in mods + list(seqs) + [module.relu]):
+    mods = [m for seq in seqs for m in seq]
+    if needs_grad(features, (p for m in mods for p in m.parameters())):
+        return None
+    if hooked(*mods, *seqs, module.relu):
         return None
     return conv_in, bn_in, pos_conv, pos_bn, conv_out, bn_out, len(seqs[2]) == 3
 
@@ -146,20 +142,16 @@ def folded_mlp_in(conv, bn):
     """mlps_in = point-wise Conv1d + eval-mode BatchNorm1d as one GEMM with bias on rows: -> {dtype: (W', b)} for float32 and
     bfloat16 rows, feats_in = features W'^T + b.  (s, b) = sparse_ops.fold_bn(bn, conv.bias); W' = s[:, None] * W formed in float64
     and rounded once to fp32; the bf16 pair is that pair rounded once more (operands and bias of a bf16 GEMM).  Cached on the
-    convolution under the weight's _version / data_ptr and the identity of fold_bn's own cached pair: an in-place update of any
-    tensor read recomputes, a second forward launches nothing."""
+    convolution (eval_route.cached) under the weight, derived from fold_bn's own cached pair: an in-place update of any tensor
+    read recomputes, a second forward launches nothing."""
     from .....sparse_ops import fold_bn
     scale, shift = fold_bn(bn, conv.bias)
-    key = (conv.weight._version, conv.weight.data_ptr(), conv.weight.device, id(scale), id(shift))
-    cached = conv.__dict__.get("_mgar_folded_in")
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    with torch.no_grad(), torch.autocast(device_type=conv.weight.device.type, enabled=False):
+
+    def build():
         w = conv.weight.detach().view(conv.out_channels, conv.in_channels).double()
         w = (scale.double()[:, None] * w).float().contiguous()
-        folded = {torch.float32: (w, shift), torch.bfloat16: (w.to(torch.bfloat16), shift.to(torch.bfloat16))}
-    conv.__dict__["_mgar_folded_in"] = (key, folded, scale, shift)   # scale / shift held: their ids stay theirs while cached
-    return folded
+        return {torch.float32: (w, shift), torch.bfloat16: (w.to(torch.bfloat16), shift.to(torch.bfloat16))}
+    return cached(conv, "_mgar_folded_in", (conv.weight,), build, derived_from=(scale, shift))
 
 
 class NeighborVoxelSAModuleMSG(nn.Module):
@@ -207,7 +199,7 @@ class NeighborVoxelSAModuleMSG(nn.Module):
         from .....bn_ops import bn_act_rows
         w = conv.weight.view(conv.out_channels, conv.in_channels)
         if features.dtype == torch.bfloat16:
-            if torch.is_grad_enabled() and (features.requires_grad or w.requires_grad):
+            if needs_grad(features, (w,)):
                 return None
             return bn_act_rows(features.contiguous() @ w.detach().to(torch.bfloat16).t(), bn, False)
         if features.dtype != torch.float32:

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from ... import sparse_ops
+from ...eval_route import bn_frozen, hooked, needs_grad
 
 
 class SparseConvTensor:
@@ -103,10 +104,6 @@ class SparseConv3d(SparseConvolution):
         super().__init__(3, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, False, indice_key)
 
 
-def _hooked(module):
-    return bool(module._forward_hooks or module._forward_pre_hooks)
-
-
 def fold_plan(mods, i, feats):
     """Whether mods[i], a SparseConvolution, runs fused with the BatchNorm1d [+ ReLU] behind it (SparseConvolution.forward_folded):
     -> (bn, relu, modules consumed: 2 or 3), or None for the unfused path.  Fused when the switch (sparse_ops.SPCONV_FOLD_BN) is on,
@@ -119,14 +116,14 @@ def fold_plan(mods, i, feats):
     conv, bn = mods[i], mods[i + 1]
     if not (isinstance(conv, SparseConvolution) and isinstance(bn, nn.BatchNorm1d)):
         return None
-    if bn.training or bn.running_mean is None or bn.running_var is None:
+    if not bn_frozen(bn):
         return None
     if not (feats.is_cuda and feats.dtype in (torch.float32, torch.bfloat16)):
         return None
-    if torch.is_grad_enabled() and (feats.requires_grad or any(p.requires_grad for m in (conv, bn) for p in m.parameters())):
+    if needs_grad(feats, (p for m in (conv, bn) for p in m.parameters())):
         return None
     relu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.ReLU)
-    if _hooked(conv) or _hooked(bn) or (relu and _hooked(mods[i + 2])):
+    if hooked(conv, bn) or (relu and hooked(mods[i + 2])):
         return None
     return bn, relu, 3 if relu else 2
 

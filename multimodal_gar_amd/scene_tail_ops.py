@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .eval_route import cached, hooked, needs_grad
 
 SCENE_TAIL_FUSE = os.environ.get("MGAR_SCENE_TAIL_FUSE", "1") != "0"
 MAX_HIDDEN = 8
@@ -19,10 +20,6 @@ MAX_HIDDEN = 8
 TailPlan = namedtuple("TailPlan", "hidden linears")
 TailPlan.__doc__ = """hidden: 0 for Linear(2, 1) + Sigmoid, H for Linear(2, H) + ReLU + Linear(H, 1) + Sigmoid; linears: the
 nn.Linear modules of D_embed in order."""
-
-
-def _hooked(module):
-    return bool(module._forward_hooks or module._forward_pre_hooks)
 
 
 def _embed_parts(d_embed):
@@ -63,9 +60,9 @@ def scene_tail_refusal(net, fused, counts=None):
         return "structure"
     if not torch.is_tensor(fused) or fused.dim() != 2 or fused.dtype != torch.float32:
         return "payload"
-    if torch.is_grad_enabled() and (fused.requires_grad or any(p.requires_grad for p in d_embed.parameters())):
+    if needs_grad(fused, d_embed.parameters()):
         return "gradient"
-    if _hooked(d_embed) or any(_hooked(m) for m in d_embed):
+    if hooked(d_embed, *d_embed):
         return "hook"
     if fused.shape[1] % 64 != 0:
         return "size"
@@ -84,20 +81,14 @@ def scene_tail_plan(net, fused, counts=None):
 
 def embed_params(d_embed, plan=None):
     """The parameter block the kernel reads, fp32 on the parameters' device: [w_v, w_g, b] for hidden == 0, else W1 (H, 2)
-    row-major, b1 (H), w2 (H), b2.  Device ops only; cached on the module, keyed on the _version / data_ptr of every tensor
-    read: a frozen model builds it once, an in-place update of any tensor rebuilds it."""
+    row-major, b1 (H), w2 (H), b2.  Device ops only; cached on the module (eval_route.cached) under every tensor read: a frozen
+    model builds it once, an in-place update of any tensor rebuilds it."""
     plan = plan or _embed_parts(d_embed)
     if plan is None:
         raise L.MgarError("scene_tail_eval: D_embed is not Linear(2,1)+Sigmoid or Linear(2,H<=8)+ReLU+Linear(H,1)+Sigmoid")
     read = [t for lin in plan.linears for t in (lin.weight, lin.bias)]
-    key = tuple((t._version, t.data_ptr(), t.device) for t in read)
-    cached = d_embed.__dict__.get("_mgar_tail_params")
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    with torch.no_grad(), torch.autocast(device_type=read[0].device.type, enabled=False):
-        block = torch.cat([t.detach().float().reshape(-1) for t in read]).contiguous()
-    d_embed.__dict__["_mgar_tail_params"] = (key, block)
-    return block
+    return cached(d_embed, "_mgar_tail_params", read,
+                  lambda: torch.cat([t.detach().float().reshape(-1) for t in read]).contiguous())
 
 
 def scene_tail_eval_fwd(fused, dg, scene_off, de_off, counts, mnp, params, hidden):
@@ -134,15 +125,11 @@ def scene_tail_eval(fused, dg, layout, d_embed):
 # ---------------------------------------------------------------------------------------------- eval-mode parameter caches
 def stacked_head_params(net, prefix, heads, ks):
     """(w1, b1, block-diagonal w2, b2) of the seven heads that share a feature, as _heads_stacked builds them on every call,
-    cached on the net per prefix and keyed on the _version / data_ptr of every tensor read: a frozen model builds them once.
+    cached (eval_route.cached) in the net's per-prefix store under every tensor read: a frozen model builds them once.
     Built by the same ops in the same order, so the values are the bits _heads_stacked computes itself."""
     read = [t for h in heads for t in (h[0].weight, h[0].bias, h[3].weight, h[3].bias)]
-    key = tuple((t._version, t.data_ptr(), t.device) for t in read)
-    store = net.__dict__.setdefault("_mgar_stacked_heads", {})
-    cached = store.get(prefix)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    with torch.no_grad():
+
+    def build():
         hid_dim = heads[0][0].out_features
         w1 = torch.cat([h[0].weight for h in heads], 0)
         b1 = torch.cat([h[0].bias for h in heads], 0)
@@ -151,9 +138,8 @@ def stacked_head_params(net, prefix, heads, ks):
         for i, (h, k) in enumerate(zip(heads, ks)):
             w2[row:row + k, i * hid_dim:(i + 1) * hid_dim] = h[3].weight
             row += k
-        b2 = torch.cat([h[3].bias for h in heads], 0)
-    store[prefix] = (key, (w1, b1, w2, b2))
-    return store[prefix][1]
+        return w1, b1, w2, torch.cat([h[3].bias for h in heads], 0)
+    return cached(net.__dict__.setdefault("_mgar_stacked_heads", {}), prefix, read, build)
 
 
 def eval_bn(bn, x):

@@ -15,6 +15,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
+from .eval_route import cached, needs_grad
 
 INT_MAX = 2 ** 31 - 1
 
@@ -226,7 +227,7 @@ def _bf16_forward(feats, w, rb):
     not bf16 rows, a gradient is needed, or a channel plan the kernel does not take): the caller runs the fp32 path."""
     if not (SPCONV_BF16 and feats.dtype == torch.bfloat16):
         return None
-    if torch.is_grad_enabled() and (feats.requires_grad or w.requires_grad):
+    if needs_grad(feats, (w,)):
         return None                                    # the gradients exist for fp32 rows only: training stays fp32
     k, cin, cout = w.shape
     nbytes = L.raw("mgar_spconv_bf16_workspace_bytes", k, cin, cout)
@@ -255,18 +256,15 @@ def fold_bn(bn, conv_bias=None):
     """An nn.BatchNorm1d with running statistics as the per-channel affine map it is in eval mode -> (scale, shift), fp32 (C,):
         scale = gamma * rsqrt(running_var + eps),   shift = beta - running_mean * scale  (+ conv_bias * scale)
     (gamma, beta = 1, 0 without affine), computed in float64 on the tensors' own device and rounded once; no host synchronisation.
-    Cached on the module, keyed on the _version and data_ptr of every tensor read: an in-place update (load_state_dict, an
-    optimiser step) or a replaced tensor recomputes, a second forward launches nothing."""
+    Cached on the module (eval_route.cached, with eps in the key): an in-place update (load_state_dict, an optimiser step) or a
+    replaced tensor recomputes, a second forward launches nothing."""
     read = [bn.running_mean, bn.running_var]
     if bn.affine:
         read += [bn.weight, bn.bias]
     if conv_bias is not None:
         read.append(conv_bias)
-    key = (float(bn.eps),) + tuple((t._version, t.data_ptr(), t.device) for t in read)
-    cached = bn.__dict__.get("_mgar_folded")
-    if cached is not None and cached[0] == key:
-        return cached[1], cached[2]
-    with torch.no_grad(), torch.autocast(device_type=bn.running_var.device.type, enabled=False):
+
+    def build():
         scale = torch.rsqrt(bn.running_var.detach().double() + float(bn.eps))
         if bn.affine:
             scale = scale * bn.weight.detach().double()
@@ -275,16 +273,15 @@ def fold_bn(bn, conv_bias=None):
             shift = shift + bn.bias.detach().double()
         if conv_bias is not None:
             shift = shift + conv_bias.detach().double() * scale
-        scale, shift = scale.float().contiguous(), shift.float().contiguous()
-    bn.__dict__["_mgar_folded"] = (key, scale, shift)
-    return scale, shift
+        return scale.float().contiguous(), shift.float().contiguous()
+    return cached(bn, "_mgar_folded", read, build, extra=(float(bn.eps),))
 
 
 def _affine_forward(feats, w, rb, epilogue):
     """The convolution with epilogue = (scale, shift, relu) in its store.  bf16 rows on a plan mgar_spconv_bf16_fwd_affine takes
     (switch on) stay bf16; everything else runs mgar_spconv_gather_gemm_affine on fp32 rows.  Forward only."""
     scale, shift, relu = epilogue
-    if torch.is_grad_enabled() and (feats.requires_grad or w.requires_grad):
+    if needs_grad(feats, (w,)):
         raise ValueError("sparse_conv3d: an epilogue is forward only; the features or the weight require a gradient")
     k, cin, cout = w.shape
     if tuple(scale.shape) != (cout,) or tuple(shift.shape) != (cout,) or scale.dtype != torch.float32 or shift.dtype != torch.float32:
